@@ -2,6 +2,14 @@
 """bench.py — Narwhal crypto hot path on MI355X: Ed25519 verifies/s (+ SHA-512 GB/s).
 
     python bench.py [--gpus N --steps K --warmup W --workload strict|sha]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps of the selected workload, checks that
+workload's outputs and prints the result line. --full adds every other leg (the secondary
+SHA-512 rate, configs 1 and 2, wire ingest, the latency legs, the CPU baselines) and the
+per-leg detail file. --dump-outputs DIR writes the arrays the last timed step left
+(DIR/<name>.npy, float32) so that two builds can be compared output for output; the inputs
+are seeded and identical from run to run.
 
 One process per GPU (torch.distributed.run for N > 1; RCCL only for the barrier and the
 max-over-ranks timing: the path shards, there is no data-path collective). Inputs are
@@ -16,7 +24,8 @@ Workloads (BASELINE.json configs):
                     semantics per item; bitmap checked against the construction.
   sha               config 3: 65,536 worker batches x 508,052 B (977 x 512 B txs,
                     bincode layout), SHA-512 digests; checked against hashlib.
-The SHA-512 rate (config 3) is also reported as a secondary field of the strict line.
+With --full the SHA-512 rate (config 3) is also reported as a secondary field of the
+strict line.
 
 Roofline work constants are SURVEY.md 8(d) (see DESIGN.md "Measurement").
 """
@@ -316,6 +325,29 @@ def timed_steps(launch, steps: int, warmup: int, world: int):
     return elapsed, kernel_ms
 
 
+# float32 bytes one run's --dump-outputs files may hold over all ranks (below 64 MB with the
+# .npy headers): the default strict run's 12.5M statuses + 1.56M bitmap bytes are 56.25 MB.
+DUMP_BUDGET = 60_000_000
+
+
+def dump_outputs(path: str, outputs: dict, rank: int, world: int) -> None:
+    """--dump-outputs: the arrays the timed call's caller receives, as the last timed step
+    left them, one <name>.npy per array (rank r of N > 1 writes <name>_r<r>.npy). float32:
+    statuses and bytes are small integers, so the conversion is exact. When the arrays
+    exceed this rank's share of DUMP_BUDGET each is written as a sample of its elements in
+    index order, the indices drawn once from a fixed seed (the same in every run)."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.size for a in outputs.values())
+    budget = DUMP_BUDGET // 4 // world
+    for name, a in outputs.items():
+        if total > budget:
+            keep = max(1, budget * a.size // total)
+            rng = np.random.Generator(np.random.PCG64(2024))
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ("" if world == 1 else f"_r{rank}") + ".npy"),
+                a.astype(np.float32))
+
+
 # ------------------------------------------------------------------------ workloads
 def run_strict(args, dev, stream, rank, world):
     """Config 4: ONE global corpus of items_per_gpu x world items (the same seeded unique
@@ -364,7 +396,8 @@ def run_strict(args, dev, stream, rank, world):
         ok = bool(t.item() == 1.0)
     del msgs, pks, sigs
     return dict(n=n, n_total=n_total, elapsed=elapsed, kernel_ms=kernel_ms, parity=ok,
-                gather_ms=gather_ms, sample=(msgs_u, pks_u, sigs_u, st[: args.unique]))
+                gather_ms=gather_ms, sample=(msgs_u, pks_u, sigs_u, st[: args.unique]),
+                outputs={"status": st, "bitmap": bitmap.cpu().numpy()})
 
 
 def run_sha(args, dev, stream, rank, world):
@@ -391,7 +424,7 @@ def run_sha(args, dev, stream, rank, world):
     ok &= all(o[i].tobytes() == expect[i % uniq] for i in range(uniq))
     del data, data_u
     return dict(n=nb, bytes=nb * W.BATCH_BYTES, elapsed=elapsed, kernel_ms=kernel_ms, parity=ok,
-                sample=(ub, expect))
+                sample=(ub, expect), outputs={"digest32": o})
 
 
 def cpu_baseline_sha(sample, seconds: float):
@@ -1340,10 +1373,25 @@ def main():
     ap.add_argument("--worker-delay", type=float, default=0.0005,
                     help="VerificationService max_delay (s) for the worker leg")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the selected workload (secondary SHA-512, "
+                         "configs 1 and 2, wire ingest, the latency legs, the CPU baselines) "
+                         "and write the per-leg detail file; the --no-* options trim this set")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write the output arrays of the last step to "
+                         "DIR/<name>.npy (float32; workloads strict and sha)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.workload not in ("strict", "sha"):
+        ap.error("--dump-outputs: only the strict and sha workloads run --steps timed steps")
+    if not args.full:
+        # a plain run measures the selected workload and nothing beside it
+        args.no_sha = args.no_cert = args.no_batch = args.no_wire = True
+        args.no_worker = args.no_service = args.no_cpu_baseline = True
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus))
     if int(os.environ.get("WORLD_SIZE", "1")) != args.gpus:
@@ -1380,6 +1428,8 @@ def main():
     result = {}
     if args.workload == "strict":
         r = run_strict(args, dev, stream, rank, world)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, r["outputs"], rank, world)
         units = r["n_total"]
         value = units / r["elapsed"] * args.steps
         achieved = r["n"] * MAC_PER_STRICT_VERIFY / (r["kernel_ms"] * 1e-3) / 1e12
@@ -1581,6 +1631,8 @@ def main():
             result["cpu_baseline"] = cpu_baseline_batch(bsample, min(5.0, args.cpu_seconds))
     else:
         s = run_sha(args, dev, stream, rank, world)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, s["outputs"], rank, world)
         gbs = s["bytes"] * world / (s["elapsed"] / args.steps) / 1e9
         kgbs = s["bytes"] / (s["kernel_ms"] * 1e-3) / 1e9
         straffic, ssrc = pmc_traffic("k_sha512_digest32", s["n"])
@@ -1601,8 +1653,9 @@ def main():
             result["cpu_baseline"] = cpu_baseline_sha(s["sample"], min(3.0, args.cpu_seconds))
     result["summary"] = summary(result)
     if rank == 0:
-        detail = write_detail(result)
-        log(f"full per-leg record: {detail}")
+        detail = write_detail(result) if args.full else None
+        if detail:
+            log(f"full per-leg record: {detail}")
         print(json.dumps(compact_line(result, detail), separators=(",", ":")), flush=True)
     if world > 1:
         dist.barrier()

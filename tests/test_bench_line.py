@@ -74,6 +74,62 @@ def test_gpus_mismatch_exits_nonzero():
     assert p.stdout.strip() == ""
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: float32 files; whole arrays (shape kept) within the budget, beyond it
+    the same seeded sample of each array on every call, inside the budget."""
+    import numpy as np
+    B = _bench()
+    st = (np.arange(5000) % 8).astype(np.int32)
+    bm = (np.arange(640) % 256).astype(np.uint8).reshape(20, 32)
+    B.dump_outputs(str(tmp_path / "a"), {"status": st, "bitmap": bm}, 0, 1)
+    a, b = np.load(tmp_path / "a" / "status.npy"), np.load(tmp_path / "a" / "bitmap.npy")
+    assert a.dtype == b.dtype == np.float32
+    assert np.array_equal(a, st) and np.array_equal(b, bm)
+    monkeypatch.setattr(B, "DUMP_BUDGET", 4 * 1128)        # a fifth of the 5,640 elements
+    for d in ("b", "c"):
+        B.dump_outputs(str(tmp_path / d), {"status": st, "bitmap": bm}, 1, 2)
+    a, b = np.load(tmp_path / "b" / "status_r1.npy"), np.load(tmp_path / "b" / "bitmap_r1.npy")
+    assert a.dtype == b.dtype == np.float32 and a.size == 500 and b.size == 64
+    assert np.isin(a, st).all() and not np.array_equal(a, st[:500])
+    assert np.array_equal(a, np.load(tmp_path / "c" / "status_r1.npy"))
+    assert np.array_equal(b, np.load(tmp_path / "c" / "bitmap_r1.npy"))
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_headline_only_and_dumps_outputs(tmp_path):
+    """A plain run: --steps timed steps of the strict leg and nothing beside it (no other
+    leg, no CPU baseline, no detail file); --dump-outputs leaves the last step's statuses and
+    verdict bitmap, which agree with each other and hold the corpus's 10 % invalid items."""
+    import numpy as np
+    n = 65536 + 37                                         # last bitmap word partly used
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
+                        "--steps", "3", "--warmup", "1", "--items-per-gpu", str(n),
+                        "--unique", "8192", "--dump-outputs", str(tmp_path)],
+                       env=dict(os.environ, NW_BENCH_DETAIL=str(tmp_path / "detail.json")),
+                       capture_output=True, text=True, timeout=110)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [x for x in p.stdout.splitlines() if x.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    r = json.loads(lines[0])
+    for k in CONTRACT:
+        assert k in r, k
+    assert r["steps"] == 3 and r["warmup"] == 1 and r["n_gpus"] == 1 and r["parity"] == "ok"
+    assert r["unit"] == "verifies/s" and r["dtype"] == "u32" and r["higher_is_better"] is True
+    assert r["value"] == pytest.approx(n / (r["ms_per_step"] * 1e-3), rel=1e-9)
+    assert "cpu_baseline" not in r and "detail" not in r
+    assert set(r["summary"]) == {"value", "unit", "parity", "roofline_frac", "issue_frac",
+                                 "cpu_baseline"} and r["summary"]["cpu_baseline"] is None
+    assert sorted(os.listdir(tmp_path)) == ["bitmap.npy", "status.npy"]
+    st, bm = np.load(tmp_path / "status.npy"), np.load(tmp_path / "bitmap.npy")
+    assert st.dtype == bm.dtype == np.float32 and st.shape == (n,)
+    assert bm.shape == ((n + 63) // 64 * 8,)
+    bits = np.unpackbits(bm.astype(np.uint8), bitorder="little")
+    assert np.array_equal(bits[:n].astype(bool), st == 0) and not bits[n:].any()
+    # 819 of the 8,192 unique items are invalid; item g of the corpus is unique[g % 8192]
+    assert int((st[:8192] != 0).sum()) == 819
+    assert np.array_equal(st[8192:], np.resize(st[:8192], n)[8192:])
+
+
 @pytest.mark.gpu
 def test_bench_gpus2_spawns_ranks():
     env = dict(os.environ, NW_BENCH_BACKEND="gloo",
@@ -88,7 +144,7 @@ def test_bench_gpus2_spawns_ranks():
                         "--certs", "2048", "--cert-unique", "512", "--committees", "4",
                         "--cert-payload-committees", "", "--batch-many", "2",
                         "--wire-frames", "512", "--wire-steps", "1",
-                        "--no-worker", "--no-service", "--no-cpu-baseline"],
+                        "--full", "--no-worker", "--no-service", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=110)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [x for x in p.stdout.splitlines() if x.startswith("{")]
@@ -118,7 +174,7 @@ def test_bench_gpus8_gloo_rehearsal():
                         "--certs", "512", "--cert-unique", "256", "--committees", "4",
                         "--cert-invalid", "0", "--cert-payload-committees", "",
                         "--batch-many", "1", "--wire-frames", "256", "--wire-steps", "1",
-                        "--no-worker", "--no-service", "--no-cpu-baseline"],
+                        "--full", "--no-worker", "--no-service", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [x for x in p.stdout.splitlines() if x.startswith("{")]

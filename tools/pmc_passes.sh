@@ -5,7 +5,7 @@
 set -o pipefail
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
-ARGS="--items-per-gpu 1048576 --steps 1 --warmup 0 --no-cpu-baseline --sha-batches 8192 $*"
+ARGS="--full --items-per-gpu 1048576 --steps 1 --warmup 0 --no-cpu-baseline --sha-batches 8192 $*"
 run() {
   local name=$1; shift
   timeout -s KILL 240 rocprofv3 --pmc "$@" --output-format csv -d gpurun_out/pmc_$name -o p \

@@ -15,13 +15,13 @@ export TMPDIR=/tmp
 TAG=${1:-run}
 OUT=$PWD/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
-PMC_ARGS="--steps 1 --warmup 0 --no-cert --no-batch --no-wire --no-service --no-worker --no-cpu-baseline"
+PMC_ARGS="--full --steps 1 --warmup 0 --no-cert --no-batch --no-wire --no-service --no-worker --no-cpu-baseline"
 
 timeout -s KILL 60 rocprofv3 -L > "$OUT/counters_available.txt" 2>&1
 echo "list rc=$?"
 
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o p \
-  -- python3 bench.py --no-cpu-baseline > "$OUT/bench_traced.json" 2> "$OUT/bench_traced.log" \
+  -- python3 bench.py --full --no-cpu-baseline > "$OUT/bench_traced.json" 2> "$OUT/bench_traced.log" \
   || { echo "trace pass failed"; exit 1; }
 echo "trace pass ok"
 
