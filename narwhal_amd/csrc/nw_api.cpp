@@ -43,6 +43,8 @@ struct DevCtx {
 struct SharedDev {
   std::mutex m;
   void* strict_ws = nullptr;   // per-lane tables of k_verify_strict (fixed size)
+  void* triage_ws = nullptr;   // the two-pass path's slice (grow-only, nw::strict_triage_bytes)
+  uint64_t triage_cap = 0;     // items
   void* ktabs = nullptr;       // committee key tables (grow-only)
   uint32_t* kok = nullptr;
   size_t kcap = 0;             // keys
@@ -275,9 +277,9 @@ int nw_dev_verify_strict_many(const void* digests, size_t digest_stride, const v
     return set_err(NW_E_INVALID_ARG, "digest_stride must be 0 or 32");
   const hipStream_t s = pick_stream(stream, c);
   nw::rt::Lease lease;
-  void* ws;
+  nw::strict_ws_t ws;
   rc = lease.acquire(t_state.device, s);
-  if (!rc) rc = lease.strict_ws(&ws);
+  if (!rc) rc = lease.strict_ws(&ws, n);
   if (rc) return rc;
   NW_HIP(nw::launch_verify_strict(static_cast<const uint32_t*>(digests),
                                   (uint32_t)(digest_stride / 4),
@@ -625,7 +627,7 @@ int cert_pipeline(int dev, const nw_committee& com, const nw_certificates& cs,
   nw::rt::Lease lease;
   void* ktabs_v = nullptr;
   uint32_t* kok = nullptr;
-  void* sws = nullptr;
+  nw::strict_ws_t sws;
   rc = lease.acquire(dev, s);
   uint32_t* ksaved = nullptr;
   uint32_t* kflag = nullptr;
@@ -637,7 +639,7 @@ int cert_pipeline(int dev, const nw_committee& com, const nw_certificates& cs,
   nw::keyspec ks{};
   if (!rc && use_keys) rc = keyed_tables_or_fallback(lease, com.nauth, &ktabs_v, &kok, &ks,
                                                      &ksaved, &kflag, &kforce, &use_keys);
-  if (!rc) rc = lease.strict_ws(&sws);
+  if (!rc) rc = lease.strict_ws(&sws, use_keys ? 0 : n);   // unkeyed: the two-pass path
   if (rc) return rc;
   nw::ge_niels_pad* ktabs = static_cast<nw::ge_niels_pad*>(ktabs_v);
   if (use_keys) {
@@ -806,14 +808,14 @@ int votes_pipeline(int dev, const nw_committee& com, size_t n, const uint8_t* id
   uint32_t* ksaved = nullptr;
   uint32_t* kflag = nullptr;
   bool kforce = true;
-  void* sws = nullptr;
+  nw::strict_ws_t sws;
   int rc = lease.acquire(dev, s);
   bool use_keys = com.nauth > 0;
   nw::keyspec ks{};
   if (!rc && use_keys)
     rc = keyed_tables_or_fallback(lease, com.nauth, &ktabs, &kok, &ks, &ksaved, &kflag,
                                   &kforce, &use_keys);
-  if (!rc) rc = lease.strict_ws(&sws);
+  if (!rc) rc = lease.strict_ws(&sws, use_keys ? 0 : n);   // unkeyed: the two-pass path
   if (rc) return rc;
   if (use_keys) {
     NW_HIP(nw::launch_key_tables(reinterpret_cast<const uint32_t*>(com.pks), com.nauth, ks,
@@ -1060,7 +1062,7 @@ int ReadLease::release() {
   return 0;
 }
 
-int Lease::strict_ws(void** out) {
+int Lease::strict_ws(nw::strict_ws_t* out, size_t n) {
   SharedDev& d = g_shared[dev_];
   if (!d.strict_ws) {
     hipError_t e = nw::table_malloc(&d.strict_ws, nw::strict_workspace_bytes());
@@ -1069,7 +1071,29 @@ int Lease::strict_ws(void** out) {
       return ::set_err(NW_E_OUT_OF_MEMORY, "hipMalloc (strict workspace)", e);
     }
   }
-  *out = d.strict_ws;
+  // the two-pass path's slice for n items: grown (at least doubled, up to the slice limit's
+  // size) after every queued launch that uses the old one has finished
+  const uint64_t slice = nw::strict_triage_slice(n);
+  if (n && slice > d.triage_cap) {
+    const uint64_t cap = std::max<uint64_t>(
+        slice, std::min<uint64_t>(2 * d.triage_cap, nw::strict_triage_slice(~0ull >> 8)));
+    if (d.triage_ws) {
+      if (d.last_valid) (void)hipEventSynchronize(d.last);
+      (void)hipFree(d.triage_ws);
+      d.triage_ws = nullptr;
+      d.triage_cap = 0;
+    }
+    hipError_t e = nw::table_malloc(&d.triage_ws, nw::strict_triage_bytes(cap));
+    if (e != hipSuccess) {
+      d.triage_ws = nullptr;
+      return ::set_err(NW_E_OUT_OF_MEMORY, "hipMalloc (strict triage slice)", e);
+    }
+    d.triage_cap = cap;
+  }
+  out->base = d.strict_ws;
+  out->triage = d.triage_ws;
+  out->triage_cap = d.triage_cap;
+  out->slice = n ? slice : 0;
   return 0;
 }
 

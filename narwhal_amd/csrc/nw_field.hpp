@@ -136,7 +136,8 @@ NW_HD void fe_join(fe& h, uint64_t a, uint64_t b) {
 
 // (Five interleaved chains of two columns each measured 4 % slower in the strict kernel: fewer
 // s_nop wait states, but at 3 waves per SIMD the other waves issue during them, and the
-// extra joins and accumulators cost instructions and spills)
+// extra joins and accumulators cost instructions and spills; three chains, columns 0-3 /
+// 4-6 / 7-9, measured 0.3 % slower, profiles/r07a/ab_ladder_carry_mul3.jsonl)
 NW_HD void fe_mul(fe& h, const fe& f, const fe& g) {
   const uint32_t f0 = f.v[0], f1 = f.v[1], f2 = f.v[2], f3 = f.v[3], f4 = f.v[4];
   const uint32_t f5 = f.v[5], f6 = f.v[6], f7 = f.v[7], f8 = f.v[8], f9 = f.v[9];

@@ -496,9 +496,9 @@ int submit_strict(int dev, const uint8_t* digests, size_t digest_stride, const u
   rc = job_run(j, o_st, o_st, end - o_st, [&]() -> int {
     // the device's shared strict workspace, ordered after its previous user (nw_runtime.h)
     nw::rt::Lease lease;
-    void* ws = nullptr;
+    nw::strict_ws_t ws;
     int lrc = lease.acquire(j->dev, j->stream);
-    if (!lrc) lrc = lease.strict_ws(&ws);
+    if (!lrc) lrc = lease.strict_ws(&ws, n);
     if (lrc) return lrc;
     JOB_HIP(nw::launch_verify_strict(reinterpret_cast<const uint32_t*>(j->dbuf + o_m),
                                      (uint32_t)(digest_stride / 4),

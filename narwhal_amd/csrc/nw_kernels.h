@@ -30,12 +30,26 @@ hipError_t launch_sha512_digest32(const uint8_t* data, const uint64_t* offsets,
 // Strict verification; workspace = strict_workspace_bytes() of device memory (per-lane
 // tables; reusable across launches on one stream).
 size_t strict_workspace_bytes();
+// The two-pass path (unkeyed launches, NW_STRICT_TRIAGE) also needs a region of
+// strict_triage_bytes(slice) for a slice of strict_triage_slice(n) items: per item the x of
+// A and R (20 words), the ladder's digit words, vneg and window count (22) and a list entry.
+// strict_triage_slice(n) = min(slice limit, n rounded up to 64); the limit is 2^24 items
+// (NW_TRIAGE_SLICE = items lowers it, e.g. to run a small input through several slices);
+// 0 when the two-pass path is off.
+uint64_t strict_triage_slice(uint64_t n);
+size_t strict_triage_bytes(uint64_t slice);
+struct strict_ws_t {
+  void* base = nullptr;       // strict_workspace_bytes()
+  void* triage = nullptr;     // strict_triage_bytes(triage_cap), or null (keyed launches)
+  uint64_t triage_cap = 0;    // items
+  uint64_t slice = 0;         // strict_triage_slice(n) of the launch this was handed out for
+};
 // keys (optional): pre-decompressed key tables with vote_key = per-item key index.
 // Builds the current device's lazily built strict tables (nw_prepare).
 hipError_t prepare_strict_tables();
 hipError_t launch_verify_strict(const uint32_t* msgs, uint32_t msg_stride_words,
                                 const uint32_t* pks, const uint32_t* sigs, uint64_t n,
-                                int32_t* status, uint64_t* bitmap, void* workspace,
+                                int32_t* status, uint64_t* bitmap, const strict_ws_t& workspace,
                                 hipStream_t stream, const struct key_tables_t* keys = nullptr);
 
 hipError_t launch_keypair(const uint32_t* seeds, uint64_t n, uint32_t* pks, hipStream_t stream);

@@ -121,6 +121,7 @@ __device__ __forceinline__ const T* opaque_ptr(const T* p) {
 // strict_verify_core's inputs for item i, fetched from global memory when needed.
 struct strict_src_global {
   static constexpr bool kPre = false;
+  static constexpr bool kScalars = false;
   const uint32_t* pk;    // 8 words
   const uint32_t* sig;   // 16 words: R || s
   const uint32_t* msg;   // 8 words
@@ -157,9 +158,13 @@ struct strict_src_global {
 
 // The same inputs with A's and R's x already decompressed (k_strict_triage): x limb k of
 // point pt (0 = A, 1 = R) of survivor q at xs[(10 pt + k) cap + q]. y is the encoding's own
-// (fe_frombytes), Z = 1, T = x y: exactly the point ge_frombytes returned.
+// (fe_frombytes), Z = 1, T = x y: exactly the point ge_frombytes returned. The same pass also
+// ran the scalar phase (nw_strict.hpp strict_triage_scalars) and stored the ladder's digit
+// word t at plane 20 + t and vneg | W << 1 at plane 41.
+constexpr uint64_t kTriagePlanes = 20 + kStrictDigitWords + 1;
 struct strict_src_pre : strict_src_global {
   static constexpr bool kPre = true;
+  static constexpr bool kScalars = true;
   const uint32_t* xs;
   uint64_t cap, q;
   __device__ bool point(int pt, ge& P) const {
@@ -173,6 +178,10 @@ struct strict_src_pre : strict_src_global {
     fe_mul(P.T, P.X, P.Y);
     return true;
   }
+  __device__ uint32_t digit_word(int t) const {
+    return opaque_ptr(xs)[(uint64_t)(20 + t) * cap + q];
+  }
+  __device__ uint32_t scalar_meta() const { return digit_word(kStrictDigitWords); }
 };
 
 // Limb planes of the pending votes of a slice: X' limb k at planes[k S + i], Z' limb k at
@@ -348,12 +357,10 @@ __global__ __launch_bounds__(256, NW_TRIAGE_WAVES) void k_strict_triage(
     const uint32_t* __restrict__ sigs, uint64_t i0, uint64_t ns, int32_t* __restrict__ status,
     uint32_t* __restrict__ xs, uint64_t cap, uint32_t* __restrict__ list,
     uint32_t* __restrict__ count) {
-  (void)msgs;
-  (void)msg_stride_words;
   const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const bool active = j < ns;
   const uint64_t i = i0 + (active ? j : 0);
-  const strict_src_global src{pks + 8 * i, sigs + 16 * i, nullptr};
+  const strict_src_global src{pks + 8 * i, sigs + 16 * i, msgs + (uint64_t)msg_stride_words * i};
   fe xa, xr;
   const int st = strict_triage(src, g_consts.sk, xa, xr);
   if (active && st != NW_OK) status[i] = st;
@@ -374,6 +381,13 @@ __global__ __launch_bounds__(256, NW_TRIAGE_WAVES) void k_strict_triage(
     xs[(uint64_t)k * cap + pos] = xa.v[k];
     xs[(uint64_t)(10 + k) * cap + pos] = xr.v[k];
   }
+  // the survivors' scalar phase, after the x limbs are stored (nothing of the decompression
+  // is live here); the lanes of rejected items have left
+  uint32_t dig[kStrictDigitWords], meta;
+  strict_triage_scalars<NW_BWIN>(src, dig, meta);
+#pragma unroll
+  for (int t = 0; t < kStrictDigitWords; ++t) xs[(uint64_t)(20 + t) * cap + pos] = dig[t];
+  xs[(uint64_t)(20 + kStrictDigitWords) * cap + pos] = meta;
 }
 
 // The list's items (persistent, as k_verify_strict): strict_verify_core on the points
@@ -988,15 +1002,6 @@ static unsigned strict_grid() {
 constexpr uint64_t kKeyedSliceMax = 1ull << 22;
 // (sized for 160-byte entries; the packed ones use 128 of each 160)
 static size_t strict_tabs_bytes() { return (size_t)strict_grid() * 256 * 16 * sizeof(ge_cached); }
-// The two-pass path's slice (k_strict_triage / k_verify_strict_pre): x of A and R (20 words)
-// and a list entry per item, after the keyed path's region (1.4 GB, once per device). Large:
-// config 4's 12.5M items are one slice, so the second pass's last, partly filled round over
-// the resident lanes comes once per launch.
-constexpr uint64_t kTriageSlice = 1ull << 24;
-static size_t strict_keyed_region_bytes() { return 4 * kKeyedSliceMax + 256; }
-size_t strict_workspace_bytes() {
-  return strict_tabs_bytes() + strict_keyed_region_bytes() + 84 * kTriageSlice + 256;
-}
 bool strict_triage_on() {   // NW_STRICT_TRIAGE=0: one pass (k_verify_strict), A/B hook
   static const bool v = [] {
     const char* e = getenv("NW_STRICT_TRIAGE");
@@ -1004,12 +1009,32 @@ bool strict_triage_on() {   // NW_STRICT_TRIAGE=0: one pass (k_verify_strict), A
   }();
   return v;
 }
+static size_t strict_keyed_region_bytes() { return 4 * kKeyedSliceMax + 256; }
+size_t strict_workspace_bytes() { return strict_tabs_bytes() + strict_keyed_region_bytes(); }
+// The two-pass path's slice (k_strict_triage / k_verify_strict_pre): kTriagePlanes words and
+// a list entry per item, then the count; a region of its own, sized for the launch
+// (172 B per item: 2.9 GB at the limit, 2.15 GB for config 4's 12.5M items). The limit is
+// large: config 4 is one slice, so the second pass's last, partly filled round over the
+// resident lanes comes once per launch.
+constexpr uint64_t kTriageSlice = 1ull << 24;
+uint64_t strict_triage_slice(uint64_t n) {
+  if (!strict_triage_on()) return 0;
+  uint64_t lim = kTriageSlice;
+  if (const char* e = getenv("NW_TRIAGE_SLICE")) {
+    const unsigned long long v = strtoull(e, nullptr, 10);
+    if (v >= 1 && v < lim) lim = v;
+  }
+  lim = (lim + 63) & ~63ull;
+  return std::min<uint64_t>(lim, (std::max<uint64_t>(n, 1) + 63) & ~63ull);
+}
+size_t strict_triage_bytes(uint64_t slice) { return 4 * (kTriagePlanes + 1) * slice + 256; }
 
 hipError_t launch_verify_strict(const uint32_t* msgs, uint32_t msg_stride_words,
                                 const uint32_t* pks, const uint32_t* sigs, uint64_t n,
-                                int32_t* status, uint64_t* bitmap, void* workspace,
+                                int32_t* status, uint64_t* bitmap, const strict_ws_t& wsp,
                                 hipStream_t stream, const key_tables_t* keys) {
   if (n == 0) return hipSuccess;
+  void* const workspace = wsp.base;
   const unsigned grid = std::min<uint64_t>(strict_grid(), grid_for(n, 256));
   const key_tables_t kt = keys ? *keys : key_tables_t{nullptr, nullptr, nullptr, {}};
   const ge_niels_pad* btw = nullptr;
@@ -1019,25 +1044,25 @@ hipError_t launch_verify_strict(const uint32_t* msgs, uint32_t msg_stride_words,
   if (eb != hipSuccess) return eb;
   const char* kf = getenv("NW_STRICT_KEYED_FAST");
   if (!kt.vote_key && strict_triage_on()) {
-    char* const ws = static_cast<char*>(workspace);
-    char* const tri = ws + strict_tabs_bytes() + strict_keyed_region_bytes();
-    uint32_t* const xs = reinterpret_cast<uint32_t*>(tri);
-    uint32_t* const list = xs + 20 * kTriageSlice;
-    uint32_t* const count = list + kTriageSlice;
-    // equal slices of at most kTriageSlice items
-    const uint64_t nsl = (n + kTriageSlice - 1) / kTriageSlice;
+    // the slice Lease::strict_ws chose for this launch (one read of NW_TRIAGE_SLICE per launch)
+    const uint64_t slice = wsp.slice;
+    if (!wsp.triage || slice == 0 || wsp.triage_cap < slice) return hipErrorInvalidValue;
+    uint32_t* const xs = static_cast<uint32_t*>(wsp.triage);
+    uint32_t* const list = xs + kTriagePlanes * slice;
+    uint32_t* const count = list + slice;
+    // equal slices of at most `slice` items
+    const uint64_t nsl = (n + slice - 1) / slice;
     const uint64_t per = (n + nsl - 1) / nsl;
     for (uint64_t i0 = 0; i0 < n; i0 += per) {
       const uint64_t ns = std::min(per, n - i0);
       hipError_t e = hipMemsetAsync(count, 0, 4, stream);
       if (e != hipSuccess) return e;
       hipLaunchKernelGGL(k_strict_triage, dim3(grid_for(ns, 256)), dim3(256), 0, stream, msgs,
-                         msg_stride_words, pks, sigs, i0, ns, status, xs, kTriageSlice, list,
-                         count);
+                         msg_stride_words, pks, sigs, i0, ns, status, xs, slice, list, count);
       hipLaunchKernelGGL(k_verify_strict_pre,
                          dim3(std::min<uint64_t>(strict_grid(), grid_for(ns, 256))), dim3(256),
                          0, stream, msgs, msg_stride_words, pks, sigs, i0, list, count, xs,
-                         kTriageSlice, status, static_cast<ge_cached_pk*>(workspace), btw);
+                         slice, status, static_cast<ge_cached_pk*>(workspace), btw);
     }
     if (bitmap)
       hipLaunchKernelGGL(k_status_bitmap, dim3(grid_for(n, 256)), dim3(256), 0, stream, status,

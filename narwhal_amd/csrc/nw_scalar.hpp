@@ -358,7 +358,10 @@ NW_HD void sc_half_split(sc_half& out, const sc& k) {
         const double yc = y + C, yd = y + D;
         if (!(yc > 0.0) || !(yd > 0.0)) break;
         const double q = f64_floor_div(x + A, yc);
-        if (q != f64_floor_div(x + B, yd)) break;
+        // q == floor((x + B) / yd) without a second division: 0 <= (x + B) - q yd < yd
+        // (integers below 2^53: the fma's result is exact whenever the test can pass)
+        const double r2 = fma(-q, yd, x + B);
+        if (r2 < 0.0 || r2 >= yd) break;
         const double r = fma(-q, y, x);
         const double nC = fma(-q, C, A), nD = fma(-q, D, B);
         if (r < lim || fabs(nC) >= 2147483648.0 || fabs(nD) >= 2147483648.0) break;

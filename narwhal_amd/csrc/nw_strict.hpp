@@ -211,6 +211,7 @@ NW_HD void build_table8(Tab* tab, const ge& P, const fe& d2) {
 // from global memory; the host self-check's returns copies of its arrays.
 struct strict_src_arrays {
   static constexpr bool kPre = false;   // A and R decompressed here (see strict_verify_core)
+  static constexpr bool kScalars = false;   // the scalar phase runs here (strict_scalar_phase)
   const uint32_t* a;
   const uint32_t* r;
   const uint32_t* s;
@@ -645,6 +646,68 @@ NW_HD int strict_keyed_comb(const Src& src, const strict_consts& K, const BComb&
 #ifndef NW_ADD_NEGC
 #define NW_ADD_NEGC 1
 #endif
+// The scalar phase of one strict verification, for k = H(R || A || M) mod l and a canonical
+// s: the half-size split u = v k (mod 8l), w = -v s mod l, and the ladder's digit words
+// dig[0..7] = u and dig[8..12] = |v| recoded to signed 4-bit digits (bias 8 per nibble),
+// dig[13..20] = w recoded to signed BW-bit digits (bdigits); vneg = v < 0 (the R digits are
+// then negated); W = this lane's ladder length in 4-bit windows: up to the highest nonzero
+// signed digit of u and |v| (digit j is nonzero iff nibble j of the recoded word is not 8),
+// at least 32 for the two 128-bit halves of w. strict_verify_core runs it in line;
+// k_strict_triage runs it for the two-pass path and stores the 21 words, vneg and W
+// (strict_triage_scalars), so the ladder kernel holds none of this code.
+constexpr int kStrictDigitWords = 21;
+template <int BW>
+NW_HD void strict_scalar_phase(uint32_t dig[kStrictDigitWords], bool& vneg, int& W, const sc& k,
+                               const sc& s) {
+  sc_half h;
+  sc_half_split(h, k);
+  // w = -v s mod l; v < 0: [v]R = [|v|](-R), taken as negated R digits (the table holds j * R)
+  sc vm, w;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) vm.w[j] = j < 5 ? h.v[j] : 0u;
+  sc_mul(w, vm, s);
+  if (!h.vneg) sc_neg(w, w);
+  // signed digits: u, |v| in 4-bit windows; w0 = w mod 2^128, w1 = w >> 128 in BW-bit
+  // windows (one signed recoding of the whole w: digit m of w1 is digit m + 128 / BW of w,
+  // the carry out of w0's top digit flows into w1's bottom one)
+  sc ur;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) ur.w[j] = h.u[j];
+  uint32_t vd[8];
+  const uint32_t bias = 0x88888888u;
+  sc_recode(dig, ur, bias);
+  sc_recode(vd, vm, bias);
+#pragma unroll
+  for (int j = 0; j < 5; ++j) dig[8 + j] = vd[j];
+  bdigits<BW>::recode(dig + 13, w);
+  uint32_t xu[8], xv[5];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) xu[j] = dig[j] ^ bias;
+#pragma unroll
+  for (int j = 0; j < 5; ++j) xv[j] = vd[j] ^ bias;
+  const int bu = bn_bits(xu, 8), bv = bn_bits(xv, 5);
+  W = ((bu > bv ? bu : bv) + 3) / 4;
+  if (W < 32) W = 32;
+  vneg = h.vneg;
+}
+
+// The triage pass's share of the two-pass path for an item that passed strict_triage (so s is
+// canonical with no high bits): k from the source (SHA-512 and the reduction mod l), the
+// scalar phase, and meta = vneg | W << 1.
+template <int BW, class Src>
+NW_HD void strict_triage_scalars(const Src& src, uint32_t dig[kStrictDigitWords], uint32_t& meta) {
+  uint32_t Sw[8], kw[8];
+  src.S(Sw);
+  src.K(kw);
+  sc s, k;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { s.w[j] = Sw[j]; k.w[j] = kw[j]; }
+  bool vneg;
+  int W;
+  strict_scalar_phase<BW>(dig, vneg, W, k, s);
+  meta = (vneg ? 1u : 0u) | ((uint32_t)W << 1);
+}
+
 // The checks before the equation, as k_strict_triage runs them (config 4 in two passes,
 // nw_kernels.hip): s's high bits and canonical form, A's and R's decompression and small
 // order, in strict_verify_core's order. Returns the status of an item that fails one of
@@ -696,7 +759,8 @@ NW_HD int strict_verify_core(const Src& src, const strict_consts& K, const BTab&
       if (pt) src.R(x); else src.A(x);
       ok = ge_frombytes(P, x, K.k);
     }
-    const bool small = small_order_by_y(P.Y, K.small_y);
+    // (kPre: every listed item passed strict_triage's small-order tests)
+    const bool small = Src::kPre ? false : small_order_by_y(P.Y, K.small_y);
     if (pt == 0) { okA = ok; smallA = small; } else { okR = ok; smallR = small; }
     if (NW_STRICT_STOP == 1) continue;
     build_table8(pt ? tabR : tabA, P, K.k.d2);
@@ -704,51 +768,49 @@ NW_HD int strict_verify_core(const Src& src, const strict_consts& K, const BTab&
   if (NW_STRICT_STOP == 1 || NW_STRICT_STOP == 2)
     return (okA ? 1 : 0) + (okR ? 2 : 0) + (smallA ? 4 : 0) + (smallR ? 8 : 0);
 
-  uint32_t Sw[8], kw[8];
-  src.S(Sw);
-  src.K(kw);
-  const bool s_high = (Sw[7] >> 29) != 0;
-  sc s, k;
+  // The scalar phase (strict_scalar_phase): in line, or, for a kScalars source, the words an
+  // earlier pass stored (k_strict_triage). For a kPre source s passed strict_triage: it is
+  // canonical with no high bits.
+  uint32_t dig[kStrictDigitWords];
+  bool vneg, s_high = false, s_canon = true;
+  int W;
+  if constexpr (Src::kScalars) {
 #pragma unroll
-  for (int j = 0; j < 8; ++j) { s.w[j] = Sw[j]; k.w[j] = kw[j]; }
-  if (NW_STRICT_STOP == 3) return (int)((kw[0] ^ kw[7] ^ Sw[0]) & 15u) + (okA ? 16 : 0);
-  const bool s_canon = sc_is_canonical(s);
-  // v < 0: [v]R = [|v|](-R), taken as negated R digits (the table holds j * R)
-  sc_half h;
-  sc_half_split(h, k);
-
-  // w = -v s mod l (s zeroed when invalid: the verdict is already decided)
-  sc vm, w;
+    for (int t = 0; t < kStrictDigitWords; ++t) {
+      const uint32_t word = src.digit_word(t);
+      if constexpr (PF::lds_digits) pf.dput(t, word); else dig[t] = word;
+    }
+    const uint32_t meta = src.scalar_meta();
+    vneg = (meta & 1u) != 0;
+    W = (int)(meta >> 1);
+    if (NW_STRICT_STOP == 3) return (int)(meta & 15u) + (okA ? 16 : 0);
+  } else {
+    uint32_t Sw[8], kw[8];
+    src.S(Sw);
+    src.K(kw);
+    sc s, k;
 #pragma unroll
-  for (int j = 0; j < 8; ++j) vm.w[j] = j < 5 ? h.v[j] : 0u;
-  if (!s_canon || s_high) {
+    for (int j = 0; j < 8; ++j) { s.w[j] = Sw[j]; k.w[j] = kw[j]; }
+    if (NW_STRICT_STOP == 3) return (int)((kw[0] ^ kw[7] ^ Sw[0]) & 15u) + (okA ? 16 : 0);
+    if constexpr (!Src::kPre) {
+      s_high = (Sw[7] >> 29) != 0;
+      s_canon = sc_is_canonical(s);
+      if (!s_canon || s_high) {   // s zeroed when invalid: the verdict is already decided
 #pragma unroll
-    for (int j = 0; j < 8; ++j) s.w[j] = 0;
+        for (int j = 0; j < 8; ++j) s.w[j] = 0;
+      }
+    }
+    strict_scalar_phase<BW>(dig, vneg, W, k, s);
+    if constexpr (PF::lds_digits) {
+#pragma unroll
+      for (int t = 0; t < kStrictDigitWords; ++t) pf.dput(t, dig[t]);
+    }
   }
-  sc_mul(w, vm, s);
-  if (!h.vneg) sc_neg(w, w);
-  // signed digits: u, |v| in 4-bit windows; w0 = w mod 2^128, w1 = w >> 128 in BW-bit
-  // windows (one signed recoding of the whole w: digit m of w1 is digit m + 128 / BW of w,
-  // the carry out of w0's top digit flows into w1's bottom one)
-  sc ur, vr;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { ur.w[j] = h.u[j]; vr.w[j] = vm.w[j]; }
-  uint32_t ud[8], vd[8], wd[8];
-  const uint32_t ubias = 0x88888888u;
-  sc_recode(ud, ur, ubias);
-  sc_recode(vd, vr, 0x88888888u);
-  BD::recode(wd, w);
-  // ladder length in 4-bit windows: up to the highest nonzero signed digit of u and |v|
-  // (digit j is nonzero iff nibble j of the recoded word is not 8), at least 32 for the
-  // two 128-bit halves of w
-  uint32_t xu[8], xv[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { xu[j] = ud[j] ^ ubias; xv[j] = vd[j] ^ 0x88888888u; }
-  const int bu = bn_bits(xu, 8), bv = bn_bits(xv, 5);
-  int W = ((bu > bv ? bu : bv) + 3) / 4;
-  if (W < 32) W = 32;
   W = wave_max(W);
-  if (NW_STRICT_STOP == 4) return W + (int)((ud[0] ^ vd[0] ^ wd[0] ^ wd[7]) & 15u) + (okR ? 64 : 0);
+  if (NW_STRICT_STOP == 4) return W + (vneg ? 16 : 0) + (okR ? 64 : 0);
+  const uint32_t* const ud = dig;
+  const uint32_t* const vd = dig + 8;
+  const uint32_t* const wd = dig + 13;
 
   // One rolled doubling and one addition routine serve every term (code size: the ladder
   // body stays inside the instruction cache). Per 4-bit window j: 4 doublings, then the
@@ -759,12 +821,6 @@ NW_HD int strict_verify_core(const Src& src, const strict_consts& K, const BTab&
   if constexpr (PF::enabled) {
     // The same additions in the same order as below; the entry of addition (j, slot) is
     // requested one addition ahead (window j's first one before its doublings).
-    if constexpr (PF::lds_digits) {
-#pragma unroll
-      for (int t = 0; t < 8; ++t) { pf.dput(t, ud[t]); pf.dput(13 + t, wd[t]); }
-#pragma unroll
-      for (int t = 0; t < 5; ++t) pf.dput(8 + t, vd[t]);
-    }
     // digit j of u / |v| (4-bit, biased by 8) and digit m of w
     auto dig4 = [&](int base, int nw, const uint32_t* arr, int j) -> int {
       if constexpr (PF::lds_digits) {
@@ -786,7 +842,7 @@ NW_HD int strict_verify_core(const Src& src, const strict_consts& K, const BTab&
         d = dig4(0, 8, ud, j);
       } else if (slot == 1) {
         d = j < 40 ? dig4(8, 5, vd, j) : 0;
-        if (h.vneg) d = -d;
+        if (vneg) d = -d;
       } else {
         const bool t1 = slot == 3 || !has0;
         d = digw(t1 ? p1 / BW : p0 / BW);
@@ -876,7 +932,7 @@ NW_HD int strict_verify_core(const Src& src, const strict_consts& K, const BTab&
         d = digit4_of(ud, 8, j);
       } else if (slot == 1) {
         d = j < 40 ? digit4_of(vd, 5, j) : 0;
-        if (h.vneg) d = -d;
+        if (vneg) d = -d;
       } else {
         // the table-0 digit first (when present), then the table-1 digit
         const bool t1 = slot == 3 || !has0;
@@ -902,6 +958,8 @@ NW_HD int strict_verify_core(const Src& src, const strict_consts& K, const BTab&
   }
   }
   const bool eq = ge_is_identity(acc);
+  // (kPre: only the equation is left, every other check passed in strict_triage)
+  if constexpr (Src::kPre) return eq ? NW_OK : NW_ERR_EQUATION;
   // Reference order: crypto/src/lib.rs:201 (s high bits), 202 (decompress A), then dalek
   // verify_strict: check_scalar, decompress R, small order (R || A), equation.
   if (s_high) return NW_ERR_S_HIGH_BITS;

@@ -183,6 +183,120 @@ int hc_verify_strict_twopass(const uint8_t pk[32], const uint8_t sig[64], const 
   return strict_verify_core<16>(src, SK, btab_wide{BTW, BTW_N}, pa, pr, id);
 }
 
+// Host model of the ladder's LDS prefetcher (nw_kernels.hip pf_lds; nw_strict.hpp pf_none for
+// the contract), so the branch of strict_verify_core the device runs (PF::enabled, digit
+// words through dput / dget, every entry requested one addition ahead) runs on the CPU too.
+// One 128-byte slot: issue() copies the entry in, get() / get_signed() read it and then
+// poison it, so a read without a matching request, or a second read of the same request,
+// yields garbage limbs instead of the right entry. The digit words are an array, garbage
+// until put.
+struct pf_host_state {
+  uint32_t slot[32];
+  uint32_t dig[kStrictDigitWords];
+  uint32_t poison_seq = 0x9e3779b9u;
+  pf_host_state() {
+    poison();
+    for (int t = 0; t < kStrictDigitWords; ++t) dig[t] = 0x5a5a5a5au + 0x01010101u * (uint32_t)t;
+  }
+  void poison() {
+    for (int i = 0; i < 32; ++i) slot[i] = (poison_seq = poison_seq * 1664525u + 1013904223u);
+  }
+};
+struct pf_host {
+  static constexpr bool enabled = true;
+  static constexpr bool lds_digits = true;
+  pf_host_state* st;
+  void dput(int k, uint32_t v) const { st->dig[k] = v; }
+  uint32_t dget(int k) const { return st->dig[k]; }
+  void issue(const void* src, int chunks) const {
+    memcpy(st->slot, src, 16 * (size_t)(chunks < 8 ? chunks : 8));
+  }
+  void read(ge_cached& e, bool niels, uint32_t a) const {
+    uint32_t p[32];
+    for (int k = 0; k < 8; ++k) memcpy(p + 4 * k, st->slot + 4 * (k < 4 ? (k ^ a) : k), 16);
+    st->poison();
+    if (niels) {
+      for (int i = 0; i < 10; ++i) {
+        e.YpX.v[i] = p[i];
+        e.YmX.v[i] = p[10 + i];
+        e.T2d.v[i] = p[20 + i];
+      }
+      return;
+    }
+    fe_unpack(e.YpX, p);
+    fe_unpack(e.YmX, p + 8);
+    fe_unpack(e.Z2, p + 16);
+    fe_unpack(e.T2d, p + 24);
+  }
+  void get(ge_cached& e, bool niels) const { read(e, niels, 0u); }
+  void get_signed(ge_cached& e, bool neg) const { read(e, false, neg ? 2u : 0u); }
+};
+// btab_lazy with the entry() the prefetch branch asks for: the entry computed into a buffer
+// of the table's own (issue() copies it at once).
+struct btab_lazy_entry {
+  btab_lazy lazy;
+  mutable ge_niels_pad buf;
+  const ge_niels_pad* entry(int h, int ad) const {
+    ge_cached e;
+    lazy(h, ad, e);
+    memset(&buf, 0, sizeof(buf));
+    fe_copy(buf.n.ypx, e.YpX);
+    fe_copy(buf.n.ymx, e.YmX);
+    fe_copy(buf.n.xy2d, e.T2d);
+    return &buf;
+  }
+  void operator()(int h, int ad, ge_cached& e) const { lazy(h, ad, e); }
+};
+
+// hc_verify_strict_half(bw < 0) through the prefetch branch (bw = -16 or -24).
+int hc_verify_strict_half_pf(const uint8_t pk[32], const uint8_t sig[64], const uint8_t k32[32],
+                             int bw) {
+  init();
+  uint32_t Aw[8], Rw[8], Sw[8], kw[8];
+  load8(Aw, pk); load8(Rw, sig); load8(Sw, sig + 32); load8(kw, k32);
+  const strict_src_arrays src{Aw, Rw, Sw, kw};
+  auto id = [](int w) { return w; };
+  ge_cached_pk pa[8], pr[8];
+  pf_host_state st;
+  if (bw == -24)
+    return strict_verify_core<24>(src, SK, btab_lazy_entry{{BT, &SK.k.d2}, {}}, pa, pr, id,
+                                  pf_host{&st});
+  return strict_verify_core<16>(src, SK, btab_wide{BTW, BTW_N}, pa, pr, id, pf_host{&st});
+}
+
+// Config 4 in two passes as the device runs them: strict_triage, then for a survivor the
+// triage-side scalar phase (strict_triage_scalars: the 21 digit words, vneg and W stored),
+// then the ladder from the stored x and the stored words (kPre and kScalars, as
+// strict_src_pre) through the prefetch branch.
+struct src_arrays_pre_scalars : src_arrays_pre {
+  static constexpr bool kScalars = true;
+  uint32_t words[kStrictDigitWords + 1];
+  uint32_t digit_word(int t) const { return words[t]; }
+  uint32_t scalar_meta() const { return words[kStrictDigitWords]; }
+};
+extern "C++" {
+template <int BW, class BTab>
+static int twopass_scalars(src_arrays_pre_scalars& src, const BTab& bt) {
+  const int st = strict_triage(static_cast<const strict_src_arrays&>(src), SK, src.xa, src.xr);
+  if (st != NW_OK) return st;
+  strict_triage_scalars<BW>(static_cast<const strict_src_arrays&>(src), src.words,
+                            src.words[kStrictDigitWords]);
+  ge_cached_pk pa[8], pr[8];
+  pf_host_state ps;
+  return strict_verify_core<BW>(src, SK, bt, pa, pr, [](int w) { return w; }, pf_host{&ps});
+}
+}
+int hc_verify_strict_twopass_scalars(const uint8_t pk[32], const uint8_t sig[64],
+                                     const uint8_t k32[32], int bw) {
+  init();
+  uint32_t Aw[8], Rw[8], Sw[8], kw[8];
+  load8(Aw, pk); load8(Rw, sig); load8(Sw, sig + 32); load8(kw, k32);
+  src_arrays_pre_scalars src{};
+  src.a = Aw; src.r = Rw; src.s = Sw; src.k = kw;
+  if (bw == -24) return twopass_scalars<24>(src, btab_lazy_entry{{BT, &SK.k.d2}, {}});
+  return twopass_scalars<16>(src, btab_wide{BTW, BTW_N});
+}
+
 // The keyed strict path (nw_strict.hpp strict_keyed_comb): the key's comb table entries
 // j * 2^(W t) A computed per lookup (keytab_lazy) by the definition the device's k_key_base /
 // k_key_tabs tabulate, the B comb likewise. Returns the status; -1 when A does not decode is reported through the

@@ -8,7 +8,12 @@ built here with one kernel change). All are loaded side by side (ctypes, RTLD_LO
 copy has its own HIP module and constants), the config-4 corpus is built once (bench.py's
 build_strict_corpus with the in-tree library), and the variants are timed interleaved
 round-robin over R rounds of K launches, so clock drift hits all of them alike. Every
-variant's statuses must equal the in-tree build's. One JSON line per variant.
+variant's statuses must equal the in-tree build's. One JSON line per variant, with the
+median of each round (rep_medians_ms): a difference between two variants counts only
+beyond the spread of one variant's own rounds.
+
+Build knobs of the two-pass path (tools/build_variant.sh NAME "-D..."): NW_TRIAGE_WAVES,
+NW_STRICT_WAVES, NW_PF_SWAP, NW_ADD_NEGC.
 """
 import argparse
 import ctypes
@@ -92,7 +97,10 @@ def main():
     for name in a.libs:
         ms = float(np.median(times[name]))
         print(json.dumps({"lib": name, "median_ms": ms, "verifies_per_s": n / ms * 1e3,
-                          "min_ms": float(np.min(times[name])), "parity": ok[name]}), flush=True)
+                          "min_ms": float(np.min(times[name])),
+                          "rep_medians_ms": [float(np.median(times[name][r * a.steps:(r + 1) * a.steps]))
+                                             for r in range(a.reps)],
+                          "parity": ok[name]}), flush=True)
 
 
 if __name__ == "__main__":
