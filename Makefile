@@ -1,5 +1,6 @@
 # Builds the MI355X engine (narwhal_amd/libnarwhal_amd.so, gfx950 only), the CPU oracle
-# (test infrastructure) and the host arithmetic check library (test infrastructure).
+# (test infrastructure) and the host check libraries of the kernels' arithmetic and of the wire
+# decoder (test infrastructure).
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Iinclude -Inarwhal_amd/csrc -Wall -Wno-unused-function
@@ -8,7 +9,7 @@ HDRS := $(wildcard $(CSRC)/*.hpp) $(CSRC)/nw_kernels.h $(CSRC)/nw_runtime.h $(CS
 LIB := narwhal_amd/libnarwhal_amd.so
 BUILD := build
 
-all: $(LIB) oracle hostcheck loadgen
+all: $(LIB) oracle hostcheck wirecheck loadgen
 
 $(BUILD)/nw_kernels.o: $(CSRC)/nw_kernels.hip $(HDRS)
 	@mkdir -p $(BUILD)
@@ -23,6 +24,10 @@ $(BUILD)/nw_cert.o: $(CSRC)/nw_cert.hip $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(BUILD)/nw_small.o: $(CSRC)/nw_small.hip $(HDRS)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(BUILD)/nw_wiredev.o: $(CSRC)/nw_wire.hip $(HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -46,7 +51,7 @@ $(BUILD)/nw_api.o: $(CSRC)/nw_api.cpp $(HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
-$(LIB): $(BUILD)/nw_kernels.o $(BUILD)/nw_batch.o $(BUILD)/nw_cert.o $(BUILD)/nw_small.o $(BUILD)/nw_api.o $(BUILD)/nw_jobs.o $(BUILD)/nw_wire.o $(BUILD)/nw_service.o $(BUILD)/nw_host.o
+$(LIB): $(BUILD)/nw_kernels.o $(BUILD)/nw_batch.o $(BUILD)/nw_cert.o $(BUILD)/nw_small.o $(BUILD)/nw_wiredev.o $(BUILD)/nw_api.o $(BUILD)/nw_jobs.o $(BUILD)/nw_wire.o $(BUILD)/nw_service.o $(BUILD)/nw_host.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 
 oracle:
@@ -54,6 +59,11 @@ oracle:
 
 hostcheck: tools/libnw_hostcheck.so
 tools/libnw_hostcheck.so: tools/hostcheck.hip $(HDRS)
+	$(HIPCC) --cuda-host-only -O2 -std=c++17 -fPIC -shared -Iinclude $< -o $@
+
+# the device wire decoder (nw_wiredec.hpp) compiled for the CPU (tests/test_wire_device_cpu.py)
+wirecheck: tools/libnw_wirecheck.so
+tools/libnw_wirecheck.so: tools/wirecheck.hip $(CSRC)/nw_wiredec.hpp
 	$(HIPCC) --cuda-host-only -O2 -std=c++17 -fPIC -shared -Iinclude $< -o $@
 
 loadgen: tools/libnw_loadgen.so
@@ -74,7 +84,7 @@ tools/ubench_valu: tools/ubench_valu.hip
 	$(HIPCC) --offload-arch=$(ARCH) -O3 $< -o $@
 
 clean:
-	rm -rf $(BUILD) $(LIB) tools/libnw_hostcheck.so tools/libnw_loadgen.so tools/service_stress tools/service_stress_tsan
+	rm -rf $(BUILD) $(LIB) tools/libnw_hostcheck.so tools/libnw_wirecheck.so tools/libnw_loadgen.so tools/service_stress tools/service_stress_tsan
 	$(MAKE) -s -C oracle clean
 
-.PHONY: all oracle hostcheck loadgen stress ubench clean
+.PHONY: all oracle hostcheck wirecheck loadgen stress ubench clean

@@ -359,6 +359,34 @@ int nw_votes_verify_many(const nw_committee* committee, const uint8_t* ids,
 int nw_primary_messages_verify_wire(const nw_committee* committee, const uint8_t* frames,
                                     const uint64_t* offsets, size_t n, int32_t* kind_out,
                                     int32_t* status_out, uint64_t* index_out);
+/* The same call with flags. flags = 0 is exactly nw_primary_messages_verify_wire with host
+ * decode: host threads parse the frames into the structure-of-arrays, which is then copied
+ * to the device. NW_WIRE_DECODE_DEVICE moves the decode to the device: the raw frames go up
+ * in one copy, a scan kernel walks every frame (same accept / reject rules, bit for bit), the
+ * host only adds up the per-frame sizes, an emit kernel writes the structure-of-arrays in
+ * device memory and the verification pipelines run where the data already is. Verdicts,
+ * kinds and indices are identical either way. Two kinds of frame are still decoded on the
+ * host, by design, and their results merged in frame order: a Header / Certificate frame
+ * whose payload keys or parents are not strictly increasing as sent (it needs the
+ * BTreeMap / BTreeSet re-sort; an honest sender never produces one, bincode writes both in
+ * key order), and a frame longer than NW_WIRE_MAX_FRAME bytes (environment, default 32768;
+ * the largest frame the reference produces at 100 authorities is ~11 KB), so that one
+ * multi-megabyte frame cannot serialise the device's walk. The device decoder runs on the
+ * calling thread's device: under nw_set_device(NW_ALL_DEVICES) the flag returns
+ * NW_E_INVALID_ARG, as the nw_dev_* calls do. Unknown flag bits: NW_E_INVALID_ARG.
+ * nw_primary_messages_verify_wire itself decodes on the host unless NW_WIRE_DECODE=device is
+ * set in the environment (read once); it then takes the device decoder whenever the calling
+ * thread runs on one device. */
+#define NW_WIRE_DECODE_DEVICE 1u
+int nw_primary_messages_verify_wire_ex(const nw_committee* committee, const uint8_t* frames,
+                                       const uint64_t* offsets, size_t n, uint32_t flags,
+                                       int32_t* kind_out, int32_t* status_out,
+                                       uint64_t* index_out);
+/* Diagnostics, like nw_path_stats: frames of the verify_wire calls so far by decoder, the
+ * device's (every frame it decided, undecodable ones included) and the host's (all frames of
+ * a host-decode call; the non-canonical and over-long frames of a device-decode call).
+ * Either pointer may be NULL. */
+int nw_wire_stats(uint64_t* device_frames, uint64_t* host_frames);
 /* Decode only (host code, no device needed): kind_out n x int32 as above; counts_out
  * (optional) n x 3 uint64: payload entries and parents after BTreeMap/BTreeSet
  * de-duplication, and votes (Header/Certificate); digests requested (CertificatesRequest). */

@@ -85,6 +85,8 @@ def lib() -> ctypes.CDLL:
         "nw_job_notify": ([P, NOTIFY_FN, P], I), "nw_job_release": ([P], None),
         "nw_path_stats": ([P, P], I),
         "nw_primary_messages_verify_wire": ([P, P, P, S, P, P, P], I),
+        "nw_primary_messages_verify_wire_ex": ([P, P, P, S, ctypes.c_uint32, P, P, P], I),
+        "nw_wire_stats": ([P, P], I),
         "nw_primary_messages_scan": ([P, P, S, P, P], I),
         "nw_service_create": ([P, S, ctypes.c_uint32, S, ctypes.POINTER(P)], I),
         "nw_service_certificate": ([P, P, S, ctypes.c_uint32, P, P, P, P, S, VERDICT_FN, P], I),

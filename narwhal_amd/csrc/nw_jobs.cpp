@@ -38,6 +38,7 @@
 #include "narwhal_amd.h"
 #include "nw_kernels.h"
 #include "nw_runtime.h"
+#include "nw_wiredec.hpp"
 
 struct nw_job {
   int dev = -1;
@@ -1267,7 +1268,296 @@ int submit_messages(const nw_committee* com, const nw_certificates* cs, int head
                  job);
 }
 
+// ---- wire ingest, decoded on the device -------------------------------------------------
+// NW_WIRE_MAX_FRAME: the longest frame the device scans (default 32 KiB; the largest frame the
+// reference can produce at N = 100 with 32 payload entries is 11,268 bytes). One lane walks
+// one frame, so the cap keeps an adversarial multi-megabyte frame from serialising a lane;
+// longer frames are the host decoder's.
+uint64_t wire_max_frame() {
+  static const uint64_t v = [] {
+    const char* e = getenv("NW_WIRE_MAX_FRAME");
+    const long long x = e && *e ? atoll(e) : 0;
+    return x > 0 ? (uint64_t)std::min<long long>(x, 1ll << 30) : (uint64_t)32768;
+  }();
+  return v;
+}
+// Lanes per frame of the emit: 16, or a whole wave once the frames are large (a certificate
+// of a 100-member committee is ~10 KB, ~2,400 word tasks). NW_WIRE_EMIT_GROUP=16|64: A/B hook.
+uint32_t wire_emit_group(uint64_t total, uint64_t n) {
+  static const int fixed = [] {
+    const char* e = getenv("NW_WIRE_EMIT_GROUP");
+    const int g = e && *e ? atoi(e) : 0;
+    return g == 16 || g == 64 ? g : 0;
+  }();
+  if (fixed) return (uint32_t)fixed;
+  return total / n >= 2048 ? 64u : 16u;
+}
+unsigned wire_stage_threads() {   // NW_WIRE_STAGE_THREADS=0..8 (default 4; 0: the caller stages)
+  static const unsigned v = [] {
+    const char* e = getenv("NW_WIRE_STAGE_THREADS");
+    const int x = e && *e ? atoi(e) : 4;
+    return (unsigned)std::min(std::max(x, 0), 8);
+  }();
+  return v;
+}
+bool wire_stamps() {   // NW_WIRE_STAMPS=1: per-phase host times of every device-decode call
+  static const bool on = [] {
+    const char* e = getenv("NW_WIRE_STAMPS");
+    return e && *e == '1';
+  }();
+  return on;
+}
+
 }  // namespace
+
+// Frames -> verdicts with the decode on the device, as one blocking job:
+//   1. frames (in chunks, each copied as soon as it is staged), offsets and the committee go
+//      H2D through the job's pinned buffer;
+//   2. k_wire_scan writes one record per frame; the records come back and the stream is
+//      synchronised, the only wait before the verdicts;
+//   3. the host's prefix sums over the records place every frame (slot within its kind,
+//      header byte offset, first vote) and give cert_pipeline the host_vote_offsets it plans
+//      with; the destinations go up and k_wire_emit writes the structure-of-arrays;
+//   4. cert_pipeline (headers), cert_pipeline (certificates) and votes_pipeline run on the
+//      job's stream over those arrays, sharing one workspace (stream order);
+//   5. the per-kind statuses and indices come back and are scattered into frame order.
+// The buffers are sized before the scan from bounds that hold for any input (a frame's
+// header bytes are shorter than the frame, a vote takes at least 72 frame bytes), and every
+// record is checked against its own frame's length before it places anything; the emit
+// checks every write against the capacities again. A reused buffer's old contents are never
+// read: every record, destination and status slot that is read was written by this call.
+// host_frames: the frames left to the host decoder (non-canonical Header / Certificate
+// frames, frames longer than the cap), whose kind / status / index this call does not write.
+int nw::rt::wire_verify_device(int dev, const nw_committee* com, const uint8_t* frames,
+                               const uint64_t* offsets, size_t n, int32_t* kind_out,
+                               int32_t* status_out, uint64_t* index_out,
+                               std::vector<uint64_t>* host_frames) {
+  namespace wd = nw::wd;
+  host_frames->clear();
+  int rc = nw::rt::check_committee(com);
+  if (rc) return rc;
+  if (n == 0) return 0;
+  const uint64_t base0 = offsets[0], total = offsets[n] - base0;
+  if (n >= (1ull << 31) || total >= (1ull << 40)) {   // beyond the records' 32-bit counts
+    for (size_t i = 0; i < n; ++i) host_frames->push_back(i);
+    return 0;
+  }
+  using clk = std::chrono::steady_clock;
+  const auto t0 = clk::now();
+  const uint64_t vbound = total / 72;
+  nw_job* j;
+  rc = job_acquire(dev, &j);
+  if (rc) return rc;
+  Packer P;
+  const size_t o_fr = P.add(total + 4), o_of = P.add(8 * (n + 1));
+  const CommitteeOffs oc = plan_committee(P, com);
+  const size_t in_end = P.off;
+  const size_t o_rec = P.add(sizeof(wd::rec_t) * n), o_dst = P.add(sizeof(wd::dst_t) * n);
+  const size_t o_st = P.add(4 * n), o_ix = P.add(8 * n), out_end = P.off;
+  // device only: the structure-of-arrays (at most 192 bytes of rows per frame besides the
+  // header bytes, 96 per vote; 32 sections' alignment slack), then the shared workspace
+  const size_t o_soa = P.add(total + 192 * n + 96 * vbound + 32 * 256);
+  const size_t o_ws = P.off;
+  const size_t ws_bound = std::max({nw::rt::cert_workspace_bytes(n, vbound),
+                                    nw::rt::cert_workspace_bytes(n, 0),
+                                    nw::rt::votes_workspace_bytes(n)});
+  rc = job_reserve(j, out_end, o_ws + ws_bound);
+  if (rc) return job_abort(j, rc);
+  char* H = j->hbuf;
+  char* D = j->dbuf;
+  // 1. inputs
+  uint64_t* ho = reinterpret_cast<uint64_t*>(H + o_of);
+  for (size_t i = 0; i <= n; ++i) ho[i] = offsets[i] - base0;
+  const nw_committee dcom = stage_committee(j, oc, com);
+  const uint64_t ctag = nw::rt::committee_hash(com);
+  memset(H + o_fr + total, 0, 4);
+  // Staging: 2 MiB chunks, each copied up as soon as it is in the pinned buffer. From 8 MiB
+  // on, up to 4 helper threads stage the chunks (chunk c by thread c mod T) while this thread
+  // queues the copies in order: one core's memcpy into pinned memory (~30 GB/s) is slower
+  // than the link.
+  constexpr uint64_t kChunk = 2ull << 20;
+  const uint64_t nchunks = (total + kChunk - 1) / kChunk;
+  const unsigned T = total >= (8ull << 20) ? wire_stage_threads() : 0;
+  std::vector<std::thread> helpers;
+  std::vector<std::atomic<uint32_t>> staged(T ? nchunks : 0);
+  for (auto& f : staged) f.store(0, std::memory_order_relaxed);
+  for (unsigned t = 0; t < T; ++t)
+    helpers.emplace_back([&, t] {
+      for (uint64_t k = t; k < nchunks; k += T) {
+        const uint64_t c = k * kChunk;
+        memcpy(H + o_fr + c, frames + base0 + c, std::min(kChunk, total - c));
+        staged[k].store(1, std::memory_order_release);
+      }
+    });
+  hipError_t e = hipSuccess;
+  for (uint64_t c = 0; c < total || c == 0; c += kChunk) {
+    const uint64_t len = std::min(kChunk, total - c);
+    if (T) {
+      while (!staged[c / kChunk].load(std::memory_order_acquire)) __builtin_ia32_pause();
+    } else if (len) {
+      memcpy(H + o_fr + c, frames + base0 + c, len);
+    }
+    const bool last = c + len >= total;
+    e = hipMemcpyAsync(D + o_fr + c, H + o_fr + c, last ? len + 4 : len, hipMemcpyHostToDevice,
+                       j->stream);
+    if (e != hipSuccess || last) break;
+  }
+  for (auto& x : helpers) x.join();   // (before any exit: they write the job's buffer)
+  if (e != hipSuccess) return job_abort(j, set_err(NW_E_DEVICE, "H2D (frames)", e));
+  e = hipMemcpyAsync(D + o_of, H + o_of, in_end - o_of, hipMemcpyHostToDevice, j->stream);
+  if (e != hipSuccess) return job_abort(j, set_err(NW_E_DEVICE, "H2D (frame offsets)", e));
+  const auto t1 = clk::now();
+  // 2. scan
+  const uint32_t* dfr = reinterpret_cast<const uint32_t*>(D + o_fr);
+  const uint64_t* dof = reinterpret_cast<const uint64_t*>(D + o_of);
+  wd::rec_t* drec = reinterpret_cast<wd::rec_t*>(D + o_rec);
+  e = nw::launch_wire_scan(dfr, dof, n, total, wire_max_frame(), drec, j->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(H + o_rec, D + o_rec, sizeof(wd::rec_t) * n, hipMemcpyDeviceToHost,
+                       j->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(j->stream);
+  if (e != hipSuccess) return job_abort(j, set_err(NW_E_DEVICE, "k_wire_scan", e));
+  const auto t2 = clk::now();
+  // 3. placement
+  const wd::rec_t* rec = reinterpret_cast<const wd::rec_t*>(H + o_rec);
+  wd::dst_t* dst = reinterpret_cast<wd::dst_t*>(H + o_dst);
+  uint64_t cnt[2] = {0, 0}, hbl[2] = {0, 0}, nvm = 0, nvotes = 0;
+  thread_local std::vector<uint64_t> cvo;
+  cvo.assign(1, 0);
+  const char* bad = nullptr;
+  for (size_t i = 0; i < n && !bad; ++i) {
+    const wd::rec_t& r = rec[i];
+    const uint64_t len = ho[i + 1] - ho[i];
+    dst[i] = wd::dst_t{0, wd::kNoSlot, 0};
+    if (r.kind == wd::kOverCap || ((r.kind == 0 || r.kind == 2) && !r.canonical)) {
+      host_frames->push_back(i);
+      continue;
+    }
+    kind_out[i] = r.kind;
+    status_out[i] = r.kind < 0 ? NW_DAG_SERIALIZATION : 0;
+    if (index_out) index_out[i] = 0;
+    if (r.kind == -1 || r.kind == NW_MSG_CERTIFICATES_REQUEST) continue;
+    if (r.kind == NW_MSG_VOTE) {
+      if (124 + (uint64_t)r.alen + r.vlen > len) bad = "vote record";   // 4 + 32 + 8 + 2 keys + 64
+      dst[i].slot = (uint32_t)nvm++;
+      continue;
+    }
+    if (r.kind != NW_MSG_HEADER && r.kind != NW_MSG_CERTIFICATE) {
+      bad = "record kind";
+      break;
+    }
+    const int k = r.kind == NW_MSG_CERTIFICATE;
+    const uint64_t hl = wd::header_len(r);
+    // what the frame itself holds: 4 + 8 + key + 8 + 8 + payload + 8 + parents + 96 (+ 8 + votes)
+    if (132 + (uint64_t)r.alen + 36 * (uint64_t)r.np + 32 * (uint64_t)r.nq +
+            (k ? 8 + 72 * (uint64_t)r.nv : 0) > len)
+      bad = "header record";
+    dst[i] = wd::dst_t{hbl[k], (uint32_t)cnt[k]++, (uint32_t)nvotes};
+    hbl[k] += hl;
+    if (k) {
+      nvotes += r.nv;
+      cvo.push_back(nvotes);
+    }
+  }
+  if (!bad && (hbl[0] + hbl[1] > total || nvotes > vbound)) bad = "record totals";
+  if (bad) return job_abort(j, set_err(NW_E_DEVICE, bad));
+  const uint64_t nh = cnt[0], nc = cnt[1];
+  Packer S;
+  S.off = o_soa;
+  wd::out_t out{};
+  for (int k = 0; k < 2; ++k) {
+    out.hb[k] = reinterpret_cast<uint8_t*>(D + S.add(hbl[k]));
+    out.hb_len[k] = hbl[k];
+    out.ho[k] = reinterpret_cast<uint64_t*>(D + S.add(8 * (cnt[k] + 1)));
+    out.pc[k] = reinterpret_cast<uint32_t*>(D + S.add(4 * cnt[k]));
+    out.ids[k] = reinterpret_cast<uint32_t*>(D + S.add(32 * cnt[k]));
+    out.sigs[k] = reinterpret_cast<uint32_t*>(D + S.add(64 * cnt[k]));
+    out.nitems[k] = (uint32_t)cnt[k];
+  }
+  out.vo = reinterpret_cast<uint64_t*>(D + S.add(8 * (nc + 1)));
+  out.vpk = reinterpret_cast<uint32_t*>(D + S.add(32 * nvotes));
+  out.vsig = reinterpret_cast<uint32_t*>(D + S.add(64 * nvotes));
+  out.nvotes = (uint32_t)nvotes;
+  out.v_ids = reinterpret_cast<uint32_t*>(D + S.add(32 * nvm));
+  out.v_rounds = reinterpret_cast<uint64_t*>(D + S.add(8 * nvm));
+  out.v_origins = reinterpret_cast<uint32_t*>(D + S.add(32 * nvm));
+  out.v_authors = reinterpret_cast<uint32_t*>(D + S.add(32 * nvm));
+  out.v_sigs = reinterpret_cast<uint32_t*>(D + S.add(64 * nvm));
+  out.nvmsg = (uint32_t)nvm;
+  const size_t ws_need = std::max({nw::rt::cert_workspace_bytes(nh, 0),
+                                   nw::rt::cert_workspace_bytes(nc, nvotes),
+                                   nw::rt::votes_workspace_bytes(nvm)});
+  if (S.off > o_ws || o_ws + ws_need > j->dcap)
+    return job_abort(j, set_err(NW_E_OUT_OF_MEMORY, "wire job buffer bound"));
+  const uint64_t nitems = nh + nc + nvm;
+  if (nitems) {
+    e = hipMemcpyAsync(D + o_dst, H + o_dst, sizeof(wd::dst_t) * n, hipMemcpyHostToDevice,
+                       j->stream);
+    if (e == hipSuccess)
+      e = nw::launch_wire_emit(dfr, dof, n, total, drec,
+                               reinterpret_cast<const wd::dst_t*>(D + o_dst), out,
+                               wire_emit_group(total, n), j->stream);
+    if (e != hipSuccess) return job_abort(j, set_err(NW_E_DEVICE, "k_wire_emit", e));
+    // 4. the checks, over the arrays where the emit put them
+    int32_t* dst_st = reinterpret_cast<int32_t*>(D + o_st);
+    uint64_t* dst_ix = reinterpret_cast<uint64_t*>(D + o_ix);
+    for (int k = 0; k < 2 && !rc; ++k) {
+      if (!cnt[k]) continue;
+      nw_certificates d{};
+      d.n = cnt[k];
+      d.header_bytes = out.hb[k];
+      d.header_offsets = out.ho[k];
+      d.payload_counts = out.pc[k];
+      d.ids = reinterpret_cast<const uint8_t*>(out.ids[k]);
+      d.header_sigs = reinterpret_cast<const uint8_t*>(out.sigs[k]);
+      d.header_bytes_len = hbl[k];
+      if (k) {
+        d.vote_offsets = out.vo;
+        d.vote_pks = reinterpret_cast<const uint8_t*>(out.vpk);
+        d.vote_sigs = reinterpret_cast<const uint8_t*>(out.vsig);
+        d.nvotes = nvotes;
+      }
+      rc = nw::rt::cert_pipeline(dev, dcom, d, k ? cvo.data() : nullptr, !k, nullptr, nullptr,
+                                 D + o_ws, dst_st + (k ? nh : 0), dst_ix + (k ? nh : 0),
+                                 j->stream, ctag, nullptr, com->pks);
+    }
+    if (!rc && nvm)
+      rc = nw::rt::votes_pipeline(dev, dcom, nvm, reinterpret_cast<const uint8_t*>(out.v_ids),
+                                  out.v_rounds, reinterpret_cast<const uint8_t*>(out.v_origins),
+                                  reinterpret_cast<const uint8_t*>(out.v_authors),
+                                  reinterpret_cast<const uint8_t*>(out.v_sigs), D + o_ws,
+                                  dst_st + nh + nc, j->stream, com->pks);
+    if (rc) return job_abort(j, rc);
+    // 5. verdicts
+    e = hipMemcpyAsync(H + o_st, D + o_st, 4 * nitems, hipMemcpyDeviceToHost, j->stream);
+    if (e == hipSuccess && nh + nc)
+      e = hipMemcpyAsync(H + o_ix, D + o_ix, 8 * (nh + nc), hipMemcpyDeviceToHost, j->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(j->stream);
+    if (e != hipSuccess) return job_abort(j, set_err(NW_E_DEVICE, "wire job", e));
+    const int32_t* st = reinterpret_cast<const int32_t*>(H + o_st);
+    const uint64_t* ix = reinterpret_cast<const uint64_t*>(H + o_ix);
+    for (size_t i = 0; i < n; ++i) {
+      if (dst[i].slot == wd::kNoSlot) continue;
+      const int32_t kd = rec[i].kind;
+      const uint64_t s = dst[i].slot + (kd == NW_MSG_CERTIFICATE ? nh : kd == NW_MSG_VOTE ? nh + nc : 0);
+      status_out[i] = st[s];
+      if (index_out && kd != NW_MSG_VOTE) index_out[i] = ix[s];
+    }
+  }
+  if (wire_stamps()) {
+    const auto t3 = clk::now();
+    auto us = [](clk::time_point a, clk::time_point b) {
+      return std::chrono::duration<double, std::micro>(b - a).count();
+    };
+    fprintf(stderr, "[narwhal_amd] wire job n=%zu bytes=%llu: stage+H2D queue %.0f us, scan "
+            "wait %.0f us, place+emit+checks %.0f us (headers %llu certs %llu votes %llu "
+            "vote msgs %llu host %zu)\n", n, (unsigned long long)total, us(t0, t1), us(t1, t2),
+            us(t2, t3), (unsigned long long)nh, (unsigned long long)nc,
+            (unsigned long long)nvotes, (unsigned long long)nvm, host_frames->size());
+  }
+  job_recycle(j);
+  return 0;
+}
 
 extern "C" {
 

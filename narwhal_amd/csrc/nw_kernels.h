@@ -260,6 +260,24 @@ hipError_t launch_vote_prepare(const cert_committee_t& com, uint64_t n, const ui
 hipError_t launch_vote_finalize(uint64_t n, const int32_t* pre, const int32_t* sig_status,
                                 int32_t* status, hipStream_t stream);
 
+// ---- wire ingest: bincode frames -> structure-of-arrays (nw_wire.hip, nw_wiredec.hpp) ----
+// frames: the frame bytes as aligned words (readable up to the next multiple of 4 past
+// total_bytes), offsets: n + 1 byte offsets from 0 to total_bytes. The scan writes one
+// wd::rec_t per frame (kind = wd::kOverCap for a frame longer than max_frame, which it does
+// not walk); the emit writes the rows of every frame whose wd::dst_t names a slot, group
+// lanes (16 or 64) per frame.
+namespace wd {
+struct rec_t;
+struct dst_t;
+struct out_t;
+}  // namespace wd
+hipError_t launch_wire_scan(const uint32_t* frames, const uint64_t* offsets, uint64_t n,
+                            uint64_t total_bytes, uint64_t max_frame, wd::rec_t* recs,
+                            hipStream_t stream);
+hipError_t launch_wire_emit(const uint32_t* frames, const uint64_t* offsets, uint64_t n,
+                            uint64_t total_bytes, const wd::rec_t* recs, const wd::dst_t* dsts,
+                            const wd::out_t& out, uint32_t group, hipStream_t stream);
+
 // ---- small jobs in one launch (nw_small.hip) --------------------------------------------
 // Header / Vote / Certificate checks of a small job (the aggregation service's latency
 // path): one launch, no copies (inputs read from and outputs written to the job's pinned

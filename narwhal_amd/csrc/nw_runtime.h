@@ -73,6 +73,16 @@ int votes_pipeline(int dev, const nw_committee& dcom, size_t n, const uint8_t* i
                    const uint8_t* sigs, void* workspace, int32_t* status, hipStream_t s,
                    const uint8_t* host_pks = nullptr);
 
+// Wire ingest with the decode on the device (nw_jobs.cpp, kernels in nw_wire.hip): n bincode
+// PrimaryMessage frames (host memory, frame i = frames[offsets[i]..offsets[i+1])) as one
+// blocking job on library device dev. Writes kind_out / status_out / index_out (optional) of
+// every frame the device decided; host_frames receives, in increasing order, the frames it
+// leaves to the host decoder (non-canonical Header / Certificate frames and frames longer
+// than NW_WIRE_MAX_FRAME), whose outputs it does not touch.
+int wire_verify_device(int dev, const nw_committee* com, const uint8_t* frames,
+                       const uint64_t* offsets, size_t n, int32_t* kind_out, int32_t* status_out,
+                       uint64_t* index_out, std::vector<uint64_t>* host_frames);
+
 // Per-device buffers shared by every caller of the library (host-buffer jobs, blocking
 // calls and nw_dev_* calls on caller streams): the strict kernel's per-lane table workspace
 // and the committee key tables. A launch sequence that uses them holds a Lease on the

@@ -22,9 +22,19 @@
 // last value wins in the map), so the `Hash for Header` bytes (messages.rs:70-84) are built
 // from the sorted, de-duplicated payload and parents, exactly as the reference hashes the
 // value it deserialised.
+//
+// Two decoders share these rules. The host decoder below (decode_frame / decode_all) parses
+// on up to 16 threads into a host structure-of-arrays, which the host-buffer calls then copy
+// to the device. With NW_WIRE_DECODE_DEVICE (nw_primary_messages_verify_wire_ex) the raw
+// frames are copied up instead and decoded by kernels (nw_wire.hip, nw_wiredec.hpp; the job
+// is nw::rt::wire_verify_device in nw_jobs.cpp); only the frames that decoder leaves to the
+// host by design (non-canonical Header / Certificate frames, frames over the cap) come back
+// here.
+#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <functional>
 #include <thread>
 #include <utility>
@@ -430,29 +440,11 @@ int check_frames(const uint8_t* frames, const uint64_t* offsets, size_t n) {
   return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int nw_primary_messages_scan(const uint8_t* frames, const uint64_t* offsets, size_t n,
-                             int32_t* kind_out, uint64_t* counts_out) {
-  int rc = check_frames(frames, offsets, n);
-  if (rc) return rc;
-  if (n && !kind_out) return set_err(NW_E_INVALID_ARG, "null kind_out");
-  thread_local Decoded d;
-  d.clear();
-  decode_all(frames, offsets, n, d, kind_out, counts_out);
-  return 0;
-}
-
-int nw_primary_messages_verify_wire(const nw_committee* committee, const uint8_t* frames,
-                                    const uint64_t* offsets, size_t n, int32_t* kind_out,
-                                    int32_t* status_out, uint64_t* index_out) {
-  int rc = nw::rt::ensure_init();
-  if (rc) return rc;
-  rc = check_frames(frames, offsets, n);
-  if (rc) return rc;
-  if (n && !status_out) return set_err(NW_E_INVALID_ARG, "null status_out");
+// Host decode (decode_all) + the host-buffer verification calls; the arguments are checked.
+int verify_wire_host(const nw_committee* committee, const uint8_t* frames,
+                     const uint64_t* offsets, size_t n, int32_t* kind_out, int32_t* status_out,
+                     uint64_t* index_out) {
+  int rc = 0;
   thread_local Decoded d;
   d.clear();
   std::vector<int32_t> kinds(n);
@@ -494,6 +486,107 @@ int nw_primary_messages_verify_wire(const nw_committee* committee, const uint8_t
     if (rc < 0) return rc;
     scatter(d.vote_of);
   }
+  return 0;
+}
+
+// Frames by decoder so far (nw_wire_stats).
+std::atomic<uint64_t> g_device_frames{0}, g_host_frames{0};
+
+bool env_decode_device() {   // NW_WIRE_DECODE=device, read once
+  static const bool on = [] {
+    const char* e = getenv("NW_WIRE_DECODE");
+    return e && strcmp(e, "device") == 0;
+  }();
+  return on;
+}
+
+// Device decode (nw::rt::wire_verify_device); the frames it leaves to the host (by design:
+// non-canonical Header / Certificate frames, frames over the cap) are gathered, verified
+// through the host path and merged in frame order.
+int verify_wire_device(int dev, const nw_committee* committee, const uint8_t* frames,
+                       const uint64_t* offsets, size_t n, int32_t* kind_out,
+                       int32_t* status_out, uint64_t* index_out) {
+  std::vector<int32_t> kinds;
+  if (!kind_out) {
+    kinds.resize(n);
+    kind_out = kinds.data();
+  }
+  std::vector<uint64_t> hf;
+  int rc = nw::rt::wire_verify_device(dev, committee, frames, offsets, n, kind_out, status_out,
+                                      index_out, &hf);
+  if (rc) return rc;
+  g_device_frames.fetch_add(n - hf.size(), std::memory_order_relaxed);
+  if (hf.empty()) return 0;
+  g_host_frames.fetch_add(hf.size(), std::memory_order_relaxed);
+  const size_t m = hf.size();
+  std::vector<uint64_t> so(m + 1, 0);
+  for (size_t k = 0; k < m; ++k) so[k + 1] = so[k] + (offsets[hf[k] + 1] - offsets[hf[k]]);
+  std::vector<uint8_t> sb(so[m] ? so[m] : 1);
+  for (size_t k = 0; k < m; ++k)
+    if (so[k + 1] > so[k]) memcpy(sb.data() + so[k], frames + offsets[hf[k]], so[k + 1] - so[k]);
+  std::vector<int32_t> sk(m), ss(m);
+  std::vector<uint64_t> si(m);
+  rc = verify_wire_host(committee, sb.data(), so.data(), m, sk.data(), ss.data(), si.data());
+  if (rc) return rc;
+  for (size_t k = 0; k < m; ++k) {
+    kind_out[hf[k]] = sk[k];
+    status_out[hf[k]] = ss[k];
+    if (index_out) index_out[hf[k]] = si[k];
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nw_primary_messages_verify_wire_ex(const nw_committee* committee, const uint8_t* frames,
+                                       const uint64_t* offsets, size_t n, uint32_t flags,
+                                       int32_t* kind_out, int32_t* status_out,
+                                       uint64_t* index_out) {
+  int rc = nw::rt::ensure_init();
+  if (rc) return rc;
+  if (flags & ~NW_WIRE_DECODE_DEVICE) return set_err(NW_E_INVALID_ARG, "unknown flags");
+  rc = check_frames(frames, offsets, n);
+  if (rc) return rc;
+  if (n && !status_out) return set_err(NW_E_INVALID_ARG, "null status_out");
+  if (!(flags & NW_WIRE_DECODE_DEVICE)) {
+    g_host_frames.fetch_add(n, std::memory_order_relaxed);
+    return verify_wire_host(committee, frames, offsets, n, kind_out, status_out, index_out);
+  }
+  if (nw::rt::thread_device() == NW_ALL_DEVICES)
+    return set_err(NW_E_INVALID_ARG, "device decode needs one device (NW_ALL_DEVICES is set)");
+  int dev = 0;
+  rc = nw::rt::select_device(&dev);
+  if (rc) return rc;
+  return verify_wire_device(dev, committee, frames, offsets, n, kind_out, status_out, index_out);
+}
+
+int nw_primary_messages_verify_wire(const nw_committee* committee, const uint8_t* frames,
+                                    const uint64_t* offsets, size_t n, int32_t* kind_out,
+                                    int32_t* status_out, uint64_t* index_out) {
+  // NW_WIRE_DECODE=device: the device decoder, wherever it applies (one device)
+  const uint32_t flags =
+      env_decode_device() && nw::rt::thread_device() != NW_ALL_DEVICES ? NW_WIRE_DECODE_DEVICE : 0u;
+  return nw_primary_messages_verify_wire_ex(committee, frames, offsets, n, flags, kind_out,
+                                            status_out, index_out);
+}
+
+int nw_wire_stats(uint64_t* device_frames, uint64_t* host_frames) {
+  if (device_frames) *device_frames = g_device_frames.load(std::memory_order_relaxed);
+  if (host_frames) *host_frames = g_host_frames.load(std::memory_order_relaxed);
+  return 0;
+}
+
+
+int nw_primary_messages_scan(const uint8_t* frames, const uint64_t* offsets, size_t n,
+                             int32_t* kind_out, uint64_t* counts_out) {
+  int rc = check_frames(frames, offsets, n);
+  if (rc) return rc;
+  if (n && !kind_out) return set_err(NW_E_INVALID_ARG, "null kind_out");
+  thread_local Decoded d;
+  d.clear();
+  decode_all(frames, offsets, n, d, kind_out, counts_out);
   return 0;
 }
 

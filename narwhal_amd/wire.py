@@ -27,7 +27,10 @@ from .messages import Certificate, Committee, Header, Vote, _p, committee_struct
 MSG_HEADER, MSG_VOTE, MSG_CERTIFICATE, MSG_CERTIFICATES_REQUEST = 0, 1, 2, 3
 DAG_SERIALIZATION = 21
 
+WIRE_DECODE_DEVICE = 1
+
 __all__ = ["serialize", "serialize_certificates_request", "verify_primary_messages", "scan",
+           "stats", "WIRE_DECODE_DEVICE",
            "MSG_HEADER", "MSG_VOTE", "MSG_CERTIFICATE", "MSG_CERTIFICATES_REQUEST",
            "DAG_SERIALIZATION"]
 
@@ -77,20 +80,41 @@ def frames_soa(frames: Sequence[bytes]) -> tuple[np.ndarray, np.ndarray]:
     return data, offs
 
 
-def verify_primary_messages(committee: Committee | dict, frames: Sequence[bytes] | tuple
+def verify_primary_messages(committee: Committee | dict, frames: Sequence[bytes] | tuple,
+                            decode: str | None = None
                             ) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
     """Decode + verify received PrimaryMessage frames on the engine.
-    Returns (kind int32[n]: MSG_* or -1, status int32[n]: 0 / NW_DAG_*, index uint64[n])."""
+    Returns (kind int32[n]: MSG_* or -1, status int32[n]: 0 / NW_DAG_*, index uint64[n]).
+    decode: "host" (host threads parse the frames), "device" (the frames are copied up raw
+    and decoded by kernels, nw_primary_messages_verify_wire_ex with NW_WIRE_DECODE_DEVICE),
+    or None: nw_primary_messages_verify_wire's default (host, unless NW_WIRE_DECODE=device is
+    set in the environment). The results are identical."""
+    if decode not in (None, "host", "device"):
+        raise ValueError(f"decode must be 'host' or 'device', not {decode!r}")
     data, offs = frames if isinstance(frames, tuple) else frames_soa(frames)
     n = len(offs) - 1
     kind = np.zeros(max(n, 1), np.int32)
     st = np.zeros(max(n, 1), np.int32)
     ix = np.zeros(max(n, 1), np.uint64)
     cc = committee_struct(committee if isinstance(committee, dict) else committee.packed())
-    check(_lib.lib().nw_primary_messages_verify_wire(ctypes.byref(cc), _p(data), _p(offs), n,
-                                                     _p(kind), _p(st), _p(ix)),
-          "nw_primary_messages_verify_wire")
+    if decode is None:
+        check(_lib.lib().nw_primary_messages_verify_wire(ctypes.byref(cc), _p(data), _p(offs), n,
+                                                         _p(kind), _p(st), _p(ix)),
+              "nw_primary_messages_verify_wire")
+    else:
+        flags = WIRE_DECODE_DEVICE if decode == "device" else 0
+        check(_lib.lib().nw_primary_messages_verify_wire_ex(ctypes.byref(cc), _p(data), _p(offs),
+                                                            n, flags, _p(kind), _p(st), _p(ix)),
+              "nw_primary_messages_verify_wire_ex")
     return kind[:n], st[:n], ix[:n]
+
+
+def stats() -> tuple[int, int]:
+    """(frames decoded on the device, frames decoded on the host) by the verify calls so far
+    (nw_wire_stats)."""
+    a, b = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    _lib.lib().nw_wire_stats(ctypes.byref(a), ctypes.byref(b))
+    return a.value, b.value
 
 
 def scan(frames: Sequence[bytes] | tuple) -> tuple[np.ndarray, np.ndarray]:
