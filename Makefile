@@ -66,6 +66,12 @@ wirecheck: tools/libnw_wirecheck.so
 tools/libnw_wirecheck.so: tools/wirecheck.hip $(CSRC)/nw_wiredec.hpp
 	$(HIPCC) --cuda-host-only -O2 -std=c++17 -fPIC -shared -Iinclude $< -o $@
 
+# the same decoder text under AddressSanitizer / UBSan over generated and mutated frames, as a
+# stand-alone CPU program (not part of `all`): make wiresan && tools/wire_canon_san
+wiresan: tools/wire_canon_san
+tools/wire_canon_san: tools/wire_canon_san.cpp $(CSRC)/nw_wiredec.hpp
+	g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all $< -o $@
+
 loadgen: tools/libnw_loadgen.so
 tools/libnw_loadgen.so: tools/nw_loadgen.cpp include/narwhal_amd.h $(LIB)
 	g++ -O2 -std=c++17 -fPIC -shared -Iinclude $< -o $@ -Lnarwhal_amd -lnarwhal_amd -Wl,-rpath,'$$ORIGIN/../narwhal_amd' -pthread
@@ -84,7 +90,7 @@ tools/ubench_valu: tools/ubench_valu.hip
 	$(HIPCC) --offload-arch=$(ARCH) -O3 $< -o $@
 
 clean:
-	rm -rf $(BUILD) $(LIB) tools/libnw_hostcheck.so tools/libnw_wirecheck.so tools/libnw_loadgen.so tools/service_stress tools/service_stress_tsan
+	rm -rf $(BUILD) $(LIB) tools/libnw_hostcheck.so tools/libnw_wirecheck.so tools/libnw_loadgen.so tools/service_stress tools/service_stress_tsan tools/wire_canon_san
 	$(MAKE) -s -C oracle clean
 
-.PHONY: all oracle hostcheck wirecheck loadgen stress ubench clean
+.PHONY: all oracle hostcheck wirecheck wiresan loadgen stress ubench clean

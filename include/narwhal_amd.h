@@ -374,10 +374,21 @@ int nw_primary_messages_verify_wire(const nw_committee* committee, const uint8_t
  * multi-megabyte frame cannot serialise the device's walk. The device decoder runs on the
  * calling thread's device: under nw_set_device(NW_ALL_DEVICES) the flag returns
  * NW_E_INVALID_ARG, as the nw_dev_* calls do. Unknown flag bits: NW_E_INVALID_ARG.
- * nw_primary_messages_verify_wire itself decodes on the host unless NW_WIRE_DECODE=device is
- * set in the environment (read once); it then takes the device decoder whenever the calling
- * thread runs on one device. */
+ * NW_WIRE_CANON_DEVICE, valid only together with NW_WIRE_DECODE_DEVICE (alone it returns
+ * NW_E_INVALID_ARG), closes the first of the two gaps: a kernel between the scan and the emit
+ * sorts and de-duplicates the payload (equal keys keep the value sent last) and the parents
+ * of every non-canonical Header / Certificate frame, and the emit writes the same rows the
+ * host decoder would have produced, so such a frame is decided on the device and
+ * nw_wire_stats counts it as a device frame. The kernel handles up to 1024 entries (payload
+ * + parents) per frame; under the default NW_WIRE_MAX_FRAME a frame holds at most 1018, so
+ * only with a raised cap can a frame exceed the bound, and it then goes to the host like a
+ * frame over the cap. Frames over the cap still go to the host.
+ * nw_primary_messages_verify_wire itself decodes on the host unless NW_WIRE_DECODE=device
+ * (NW_WIRE_DECODE_DEVICE) or NW_WIRE_DECODE=device-canon (both flags) is set in the
+ * environment (read once); it then takes the device decoder whenever the calling thread runs
+ * on one device. */
 #define NW_WIRE_DECODE_DEVICE 1u
+#define NW_WIRE_CANON_DEVICE 2u
 int nw_primary_messages_verify_wire_ex(const nw_committee* committee, const uint8_t* frames,
                                        const uint64_t* offsets, size_t n, uint32_t flags,
                                        int32_t* kind_out, int32_t* status_out,

@@ -1292,6 +1292,17 @@ uint32_t wire_emit_group(uint64_t total, uint64_t n) {
   if (fixed) return (uint32_t)fixed;
   return total / n >= 2048 ? 64u : 16u;
 }
+// Lanes per frame of the canonicalisation: a wave, or four once the frames are large (its walks
+// are quadratic in a frame's entries). NW_WIRE_CANON_LANES=64|256: A/B hook.
+uint32_t wire_canon_lanes(uint64_t total, uint64_t n) {
+  static const int fixed = [] {
+    const char* e = getenv("NW_WIRE_CANON_LANES");
+    const int g = e && *e ? atoi(e) : 0;
+    return g == 64 || g == 256 ? g : 0;
+  }();
+  if (fixed) return (uint32_t)fixed;
+  return total / n >= 2048 ? 256u : 64u;
+}
 unsigned wire_stage_threads() {   // NW_WIRE_STAGE_THREADS=0..8 (default 4; 0: the caller stages)
   static const unsigned v = [] {
     const char* e = getenv("NW_WIRE_STAGE_THREADS");
@@ -1328,8 +1339,16 @@ bool wire_stamps() {   // NW_WIRE_STAMPS=1: per-phase host times of every device
 // read: every record, destination and status slot that is read was written by this call.
 // host_frames: the frames left to the host decoder (non-canonical Header / Certificate
 // frames, frames longer than the cap), whose kind / status / index this call does not write.
+// canon: k_wire_canon runs between the scan and the read-back (no second wait: its canon_t
+// array lies behind the records and comes back in the same copy) and a non-canonical frame of
+// at most wd::kCanonMax entries gets a slot like a canonical one, its header bytes sized by
+// the kept counts; only the frames over that bound and over the cap are left to the host.
+// The canon_t array (n entries) and the order scratch (wd::canon_list_words(total) words,
+// see nw_wiredec.hpp for why that holds every frame's list) are sized before the scan;
+// k_wire_canon writes every canon_t, and an order word is read only below the kept counts it
+// wrote in this call.
 int nw::rt::wire_verify_device(int dev, const nw_committee* com, const uint8_t* frames,
-                               const uint64_t* offsets, size_t n, int32_t* kind_out,
+                               const uint64_t* offsets, size_t n, bool canon, int32_t* kind_out,
                                int32_t* status_out, uint64_t* index_out,
                                std::vector<uint64_t>* host_frames) {
   namespace wd = nw::wd;
@@ -1352,11 +1371,15 @@ int nw::rt::wire_verify_device(int dev, const nw_committee* com, const uint8_t* 
   const size_t o_fr = P.add(total + 4), o_of = P.add(8 * (n + 1));
   const CommitteeOffs oc = plan_committee(P, com);
   const size_t in_end = P.off;
-  const size_t o_rec = P.add(sizeof(wd::rec_t) * n), o_dst = P.add(sizeof(wd::dst_t) * n);
+  const size_t o_rec = P.add(sizeof(wd::rec_t) * n);
+  const size_t o_can = canon ? P.add(sizeof(wd::canon_t) * n) : 0;   // (behind the records)
+  const size_t o_dst = P.add(sizeof(wd::dst_t) * n);
   const size_t o_st = P.add(4 * n), o_ix = P.add(8 * n), out_end = P.off;
   // device only: the structure-of-arrays (at most 192 bytes of rows per frame besides the
   // header bytes, 96 per vote; 32 sections' alignment slack), then the shared workspace
   const size_t o_soa = P.add(total + 192 * n + 96 * vbound + 32 * 256);
+  const uint64_t ord_cap = canon ? wd::canon_list_words(total) : 0;
+  const size_t o_ord = canon ? P.add(4 * ord_cap) : 0;
   const size_t o_ws = P.off;
   const size_t ws_bound = std::max({nw::rt::cert_workspace_bytes(n, vbound),
                                     nw::rt::cert_workspace_bytes(n, 0),
@@ -1367,7 +1390,11 @@ int nw::rt::wire_verify_device(int dev, const nw_committee* com, const uint8_t* 
   char* D = j->dbuf;
   // 1. inputs
   uint64_t* ho = reinterpret_cast<uint64_t*>(H + o_of);
-  for (size_t i = 0; i <= n; ++i) ho[i] = offsets[i] - base0;
+  uint64_t maxlen = 0;
+  for (size_t i = 0; i <= n; ++i) {
+    ho[i] = offsets[i] - base0;
+    if (i) maxlen = std::max(maxlen, ho[i] - ho[i - 1]);
+  }
   const nw_committee dcom = stage_committee(j, oc, com);
   const uint64_t ctag = nw::rt::committee_hash(com);
   memset(H + o_fr + total, 0, 4);
@@ -1411,17 +1438,29 @@ int nw::rt::wire_verify_device(int dev, const nw_committee* com, const uint8_t* 
   const uint32_t* dfr = reinterpret_cast<const uint32_t*>(D + o_fr);
   const uint64_t* dof = reinterpret_cast<const uint64_t*>(D + o_of);
   wd::rec_t* drec = reinterpret_cast<wd::rec_t*>(D + o_rec);
+  wd::canon_t* dcan = canon ? reinterpret_cast<wd::canon_t*>(D + o_can) : nullptr;
+  uint32_t* dord = canon ? reinterpret_cast<uint32_t*>(D + o_ord) : nullptr;
   e = nw::launch_wire_scan(dfr, dof, n, total, wire_max_frame(), drec, j->stream);
+  if (e == hipSuccess && canon)
+    // (LDS for as many entries as the longest scanned frame can hold, 32 bytes each at least)
+    e = nw::launch_wire_canon(dfr, dof, n, total, drec, dcan, dord, ord_cap,
+                              wire_canon_lanes(total, n),
+                              (uint32_t)std::min<uint64_t>(
+                                  std::max<uint64_t>(std::min(maxlen, wire_max_frame()) / 32, 1),
+                                  wd::kCanonMax),
+                              j->stream);
   if (e == hipSuccess)
-    e = hipMemcpyAsync(H + o_rec, D + o_rec, sizeof(wd::rec_t) * n, hipMemcpyDeviceToHost,
-                       j->stream);
+    e = hipMemcpyAsync(H + o_rec, D + o_rec,
+                       canon ? o_can + sizeof(wd::canon_t) * n - o_rec : sizeof(wd::rec_t) * n,
+                       hipMemcpyDeviceToHost, j->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(j->stream);
   if (e != hipSuccess) return job_abort(j, set_err(NW_E_DEVICE, "k_wire_scan", e));
   const auto t2 = clk::now();
   // 3. placement
   const wd::rec_t* rec = reinterpret_cast<const wd::rec_t*>(H + o_rec);
+  const wd::canon_t* can = canon ? reinterpret_cast<const wd::canon_t*>(H + o_can) : nullptr;
   wd::dst_t* dst = reinterpret_cast<wd::dst_t*>(H + o_dst);
-  uint64_t cnt[2] = {0, 0}, hbl[2] = {0, 0}, nvm = 0, nvotes = 0;
+  uint64_t cnt[2] = {0, 0}, hbl[2] = {0, 0}, nvm = 0, nvotes = 0, ncanon = 0;
   thread_local std::vector<uint64_t> cvo;
   cvo.assign(1, 0);
   const char* bad = nullptr;
@@ -1429,7 +1468,8 @@ int nw::rt::wire_verify_device(int dev, const nw_committee* com, const uint8_t* 
     const wd::rec_t& r = rec[i];
     const uint64_t len = ho[i + 1] - ho[i];
     dst[i] = wd::dst_t{0, wd::kNoSlot, 0};
-    if (r.kind == wd::kOverCap || ((r.kind == 0 || r.kind == 2) && !r.canonical)) {
+    const bool noncanon = (r.kind == 0 || r.kind == 2) && !r.canonical;
+    if (r.kind == wd::kOverCap || (noncanon && (!canon || can[i].state == wd::kCanonOver))) {
       host_frames->push_back(i);
       continue;
     }
@@ -1447,7 +1487,15 @@ int nw::rt::wire_verify_device(int dev, const nw_committee* com, const uint8_t* 
       break;
     }
     const int k = r.kind == NW_MSG_CERTIFICATE;
-    const uint64_t hl = wd::header_len(r);
+    uint64_t hl = wd::header_len(r);
+    if (noncanon) {   // the kept counts: at most the raw ones, and none only where none was sent
+      const wd::canon_t& c = can[i];
+      if (c.state != wd::kCanonDone || c.np_u > r.np || c.nq_u > r.nq || (r.np && !c.np_u) ||
+          (r.nq && !c.nq_u))
+        bad = "canon record";
+      hl = wd::header_len(c);
+      ++ncanon;
+    }
     // what the frame itself holds: 4 + 8 + key + 8 + 8 + payload + 8 + parents + 96 (+ 8 + votes)
     if (132 + (uint64_t)r.alen + 36 * (uint64_t)r.np + 32 * (uint64_t)r.nq +
             (k ? 8 + 72 * (uint64_t)r.nv : 0) > len)
@@ -1495,8 +1543,8 @@ int nw::rt::wire_verify_device(int dev, const nw_committee* com, const uint8_t* 
                        j->stream);
     if (e == hipSuccess)
       e = nw::launch_wire_emit(dfr, dof, n, total, drec,
-                               reinterpret_cast<const wd::dst_t*>(D + o_dst), out,
-                               wire_emit_group(total, n), j->stream);
+                               reinterpret_cast<const wd::dst_t*>(D + o_dst), dcan, dord,
+                               ord_cap, out, wire_emit_group(total, n), j->stream);
     if (e != hipSuccess) return job_abort(j, set_err(NW_E_DEVICE, "k_wire_emit", e));
     // 4. the checks, over the arrays where the emit put them
     int32_t* dst_st = reinterpret_cast<int32_t*>(D + o_st);
@@ -1551,9 +1599,10 @@ int nw::rt::wire_verify_device(int dev, const nw_committee* com, const uint8_t* 
     };
     fprintf(stderr, "[narwhal_amd] wire job n=%zu bytes=%llu: stage+H2D queue %.0f us, scan "
             "wait %.0f us, place+emit+checks %.0f us (headers %llu certs %llu votes %llu "
-            "vote msgs %llu host %zu)\n", n, (unsigned long long)total, us(t0, t1), us(t1, t2),
-            us(t2, t3), (unsigned long long)nh, (unsigned long long)nc,
-            (unsigned long long)nvotes, (unsigned long long)nvm, host_frames->size());
+            "vote msgs %llu canonicalised %llu host %zu)\n", n, (unsigned long long)total,
+            us(t0, t1), us(t1, t2), us(t2, t3), (unsigned long long)nh, (unsigned long long)nc,
+            (unsigned long long)nvotes, (unsigned long long)nvm, (unsigned long long)ncanon,
+            host_frames->size());
   }
   job_recycle(j);
   return 0;

@@ -265,18 +265,29 @@ hipError_t launch_vote_finalize(uint64_t n, const int32_t* pre, const int32_t* s
 // total_bytes), offsets: n + 1 byte offsets from 0 to total_bytes. The scan writes one
 // wd::rec_t per frame (kind = wd::kOverCap for a frame longer than max_frame, which it does
 // not walk); the emit writes the rows of every frame whose wd::dst_t names a slot, group
-// lanes (16 or 64) per frame.
+// lanes (16 or 64) per frame. The canon kernel (after the scan) writes one wd::canon_t per
+// frame and, for every non-canonical Header / Certificate frame of at most wd::kCanonMax
+// entries, its order list into `order` (order_cap = wd::canon_list_words(total_bytes) words),
+// with 64 or 256 lanes per workgroup and LDS for lds_entries (1..wd::kCanonMax) entries, no
+// fewer than any scanned frame of the call can hold (a frame of len bytes: len / 32); with cans != nullptr the emit writes those frames' rows
+// through their lists.
 namespace wd {
 struct rec_t;
 struct dst_t;
 struct out_t;
+struct canon_t;
 }  // namespace wd
 hipError_t launch_wire_scan(const uint32_t* frames, const uint64_t* offsets, uint64_t n,
                             uint64_t total_bytes, uint64_t max_frame, wd::rec_t* recs,
                             hipStream_t stream);
 hipError_t launch_wire_emit(const uint32_t* frames, const uint64_t* offsets, uint64_t n,
                             uint64_t total_bytes, const wd::rec_t* recs, const wd::dst_t* dsts,
+                            const wd::canon_t* cans, const uint32_t* order, uint64_t order_cap,
                             const wd::out_t& out, uint32_t group, hipStream_t stream);
+hipError_t launch_wire_canon(const uint32_t* frames, const uint64_t* offsets, uint64_t n,
+                             uint64_t total_bytes, const wd::rec_t* recs, wd::canon_t* cans,
+                             uint32_t* order, uint64_t order_cap, uint32_t lanes,
+                             uint32_t lds_entries, hipStream_t stream);
 
 // ---- small jobs in one launch (nw_small.hip) --------------------------------------------
 // Header / Vote / Certificate checks of a small job (the aggregation service's latency

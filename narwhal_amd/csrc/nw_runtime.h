@@ -78,10 +78,13 @@ int votes_pipeline(int dev, const nw_committee& dcom, size_t n, const uint8_t* i
 // blocking job on library device dev. Writes kind_out / status_out / index_out (optional) of
 // every frame the device decided; host_frames receives, in increasing order, the frames it
 // leaves to the host decoder (non-canonical Header / Certificate frames and frames longer
-// than NW_WIRE_MAX_FRAME), whose outputs it does not touch.
+// than NW_WIRE_MAX_FRAME), whose outputs it does not touch. canon (NW_WIRE_CANON_DEVICE): the
+// non-canonical frames of at most wd::kCanonMax entries are sorted and de-duplicated on the
+// device and decided there too.
 int wire_verify_device(int dev, const nw_committee* com, const uint8_t* frames,
-                       const uint64_t* offsets, size_t n, int32_t* kind_out, int32_t* status_out,
-                       uint64_t* index_out, std::vector<uint64_t>* host_frames);
+                       const uint64_t* offsets, size_t n, bool canon, int32_t* kind_out,
+                       int32_t* status_out, uint64_t* index_out,
+                       std::vector<uint64_t>* host_frames);
 
 // Per-device buffers shared by every caller of the library (host-buffer jobs, blocking
 // calls and nw_dev_* calls on caller streams): the strict kernel's per-lane table workspace

@@ -29,7 +29,9 @@
 // frames are copied up instead and decoded by kernels (nw_wire.hip, nw_wiredec.hpp; the job
 // is nw::rt::wire_verify_device in nw_jobs.cpp); only the frames that decoder leaves to the
 // host by design (non-canonical Header / Certificate frames, frames over the cap) come back
-// here.
+// here. With NW_WIRE_CANON_DEVICE as well the device sorts and de-duplicates the
+// non-canonical frames itself and only frames over the cap (or over wd::kCanonMax entries,
+// which takes a raised cap) come back.
 #include <stdlib.h>
 #include <string.h>
 
@@ -492,19 +494,21 @@ int verify_wire_host(const nw_committee* committee, const uint8_t* frames,
 // Frames by decoder so far (nw_wire_stats).
 std::atomic<uint64_t> g_device_frames{0}, g_host_frames{0};
 
-bool env_decode_device() {   // NW_WIRE_DECODE=device, read once
-  static const bool on = [] {
+uint32_t env_decode_flags() {   // NW_WIRE_DECODE=device | device-canon, read once
+  static const uint32_t flags = [] {
     const char* e = getenv("NW_WIRE_DECODE");
-    return e && strcmp(e, "device") == 0;
+    if (e && strcmp(e, "device") == 0) return NW_WIRE_DECODE_DEVICE;
+    if (e && strcmp(e, "device-canon") == 0) return NW_WIRE_DECODE_DEVICE | NW_WIRE_CANON_DEVICE;
+    return 0u;
   }();
-  return on;
+  return flags;
 }
 
 // Device decode (nw::rt::wire_verify_device); the frames it leaves to the host (by design:
-// non-canonical Header / Certificate frames, frames over the cap) are gathered, verified
-// through the host path and merged in frame order.
+// non-canonical Header / Certificate frames unless canon is set, frames over the cap) are
+// gathered, verified through the host path and merged in frame order.
 int verify_wire_device(int dev, const nw_committee* committee, const uint8_t* frames,
-                       const uint64_t* offsets, size_t n, int32_t* kind_out,
+                       const uint64_t* offsets, size_t n, bool canon, int32_t* kind_out,
                        int32_t* status_out, uint64_t* index_out) {
   std::vector<int32_t> kinds;
   if (!kind_out) {
@@ -512,8 +516,8 @@ int verify_wire_device(int dev, const nw_committee* committee, const uint8_t* fr
     kind_out = kinds.data();
   }
   std::vector<uint64_t> hf;
-  int rc = nw::rt::wire_verify_device(dev, committee, frames, offsets, n, kind_out, status_out,
-                                      index_out, &hf);
+  int rc = nw::rt::wire_verify_device(dev, committee, frames, offsets, n, canon, kind_out,
+                                      status_out, index_out, &hf);
   if (rc) return rc;
   g_device_frames.fetch_add(n - hf.size(), std::memory_order_relaxed);
   if (hf.empty()) return 0;
@@ -546,7 +550,10 @@ int nw_primary_messages_verify_wire_ex(const nw_committee* committee, const uint
                                        uint64_t* index_out) {
   int rc = nw::rt::ensure_init();
   if (rc) return rc;
-  if (flags & ~NW_WIRE_DECODE_DEVICE) return set_err(NW_E_INVALID_ARG, "unknown flags");
+  if (flags & ~(NW_WIRE_DECODE_DEVICE | NW_WIRE_CANON_DEVICE))
+    return set_err(NW_E_INVALID_ARG, "unknown flags");
+  if ((flags & NW_WIRE_CANON_DEVICE) && !(flags & NW_WIRE_DECODE_DEVICE))
+    return set_err(NW_E_INVALID_ARG, "NW_WIRE_CANON_DEVICE needs NW_WIRE_DECODE_DEVICE");
   rc = check_frames(frames, offsets, n);
   if (rc) return rc;
   if (n && !status_out) return set_err(NW_E_INVALID_ARG, "null status_out");
@@ -559,15 +566,15 @@ int nw_primary_messages_verify_wire_ex(const nw_committee* committee, const uint
   int dev = 0;
   rc = nw::rt::select_device(&dev);
   if (rc) return rc;
-  return verify_wire_device(dev, committee, frames, offsets, n, kind_out, status_out, index_out);
+  return verify_wire_device(dev, committee, frames, offsets, n,
+                            (flags & NW_WIRE_CANON_DEVICE) != 0, kind_out, status_out, index_out);
 }
 
 int nw_primary_messages_verify_wire(const nw_committee* committee, const uint8_t* frames,
                                     const uint64_t* offsets, size_t n, int32_t* kind_out,
                                     int32_t* status_out, uint64_t* index_out) {
-  // NW_WIRE_DECODE=device: the device decoder, wherever it applies (one device)
-  const uint32_t flags =
-      env_decode_device() && nw::rt::thread_device() != NW_ALL_DEVICES ? NW_WIRE_DECODE_DEVICE : 0u;
+  // NW_WIRE_DECODE=device | device-canon: the device decoder, wherever it applies (one device)
+  const uint32_t flags = nw::rt::thread_device() != NW_ALL_DEVICES ? env_decode_flags() : 0u;
   return nw_primary_messages_verify_wire_ex(committee, frames, offsets, n, flags, kind_out,
                                             status_out, index_out);
 }

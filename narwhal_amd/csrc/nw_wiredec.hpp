@@ -13,7 +13,8 @@
 //         `Hash for Header` bytes are the frame's own payload and parent bytes in place, and
 //         no sort is needed. Non-canonical Header / Certificate frames (which an honest
 //         sender never produces: bincode writes a BTreeMap / BTreeSet in key order) are left
-//         to the host decoder.
+//         to the host decoder, unless the caller asks for the canonicalisation below
+//         (canon_*, emit_lane_canon), which sorts and de-duplicates them on the device.
 //   emit  writes the item's structure-of-arrays rows as 4-byte words, cooperatively: the
 //         frame's output is a list of word tasks, lane l of a group of G takes tasks l,
 //         l + G, ..., so contiguous lanes write contiguous words. Every destination is
@@ -334,6 +335,203 @@ NW_HD void emit_lane(const uint32_t* w, uint64_t off, uint64_t len, const rec_t&
     else if (t < pw) hb[t] = rd_u32(w, pay + 4 * (uint64_t)(t - 10));
     else if (t < hw) hb[t] = rd_u32(w, par + 4 * (uint64_t)(t - pw));
     else if (t < hw + 8) o.ids[k][8 * (uint64_t)d.slot + (t - hw)] = rd_u32(w, idp + 4 * (t - hw));
+    else if (t < hw + 24)
+      o.sigs[k][16 * (uint64_t)d.slot + (t - hw - 8)] = rd_u32(w, idp + 32 + 4 * (t - hw - 8));
+    else {
+      const uint32_t v = (t - hw - 24) / 24, j = (t - hw - 24) % 24;
+      uint64_t vp, L;
+      if (r.vlen) {
+        L = r.vlen;
+        vp = vts + (uint64_t)v * (8 + L + 64);
+      } else {
+        for (; wv < v; ++wv) {
+          if (wpos + 8 > off + len) return;
+          const uint64_t l = rd_u64(w, wpos);
+          if (l > len) return;
+          wpos += 8 + l + 64;
+        }
+        if (wpos + 8 > off + len) return;
+        vp = wpos;
+        L = rd_u64(w, vp);
+      }
+      if (L > len || vp + 8 + L + 64 > off + len) return;
+      const uint64_t vs = (uint64_t)d.vote0 + v;
+      if (j < 8) o.vpk[8 * vs + j] = b64_word(w, vp + 8, j);
+      else o.vsig[16 * vs + (j - 8)] = rd_u32(w, vp + 8 + L + 4 * (j - 8));
+    }
+  }
+}
+
+// ---- canonicalisation of non-canonical Header / Certificate frames --------------------
+// BTreeMap / BTreeSet deserialisation of a frame whose payload keys or parents are not
+// strictly increasing as sent: sort each section by key (32-byte lexicographic, unsigned),
+// keep one entry per key, in the payload the one that comes last in wire order (its worker
+// id wins). Nothing is moved: the result is an order list, one index per kept entry that
+// says which wire entry supplies that output position, and the emit reads the frame through
+// it. A group of lanes works on one frame, in phases with a barrier between them that the
+// caller supplies (the kernel: __syncthreads(); the CPU check: a loop over the lanes per
+// phase):
+//   canon_stage  the keys of both sections go into `keys`, 8 words per entry, each word
+//                byte-swapped, so that the lexicographic compare is an unsigned word compare,
+//                most significant word first;
+//   canon_mark   entry i is dropped if a later entry of its section has the same key;
+//   canon_rank   a kept entry's output position is the number of kept entries of its section
+//                with a smaller key; one lane per section counts the kept entries.
+// Lane l of L takes entries l, l + L, ...; in the walks over j every lane reads the same
+// key, a broadcast in LDS. O(n^2 / L) compares of at most 8 words, n <= kCanonMax.
+//
+// The order list of the frame at byte offset off starts at word ceil(off / 32) of a scratch
+// of ceil(total / 32) + 1 words (total = all frames' bytes): payload positions at [0, np_u),
+// parent positions at [np, np + nq_u), np the raw payload count, so that no phase needs a
+// count that another lane of the same phase produces. A frame holds 132 bytes besides its
+// entries and every entry takes at least 32, so len >= 32 (np + nq) + 132 and
+// ceil(off / 32) + np + nq <= ceil(off / 32) + floor(len / 32) <= ceil((off + len) / 32): the
+// lists of two frames cannot overlap and the last one ends inside the scratch, for any
+// input. Every write is checked against the scratch's capacity all the same.
+constexpr uint32_t kCanonMax = 1024;   // entries per frame (payload + parents) the device sorts
+enum : uint32_t {
+  kCanonNone = 0,   // not applicable: not a Header / Certificate, does not decode, or canonical
+  kCanonDone = 1,   // canonicalised: np_u / nq_u and the order list are valid
+  kCanonOver = 2,   // more than kCanonMax entries: the host decodes it
+};
+// One frame's result, beside its rec_t (16 bytes).
+struct canon_t {
+  uint32_t np_u, nq_u;   // kept payload entries, kept parents
+  uint32_t state;        // kCanon*
+  uint32_t reserved;     // 0
+};
+// What the phases of one frame share.
+struct canon_job_t {
+  const uint32_t* w;
+  uint64_t pay, par;     // absolute byte address of the first payload entry / first parent
+  uint32_t np, nq;       // raw counts
+  uint64_t list, cap;    // first word of the frame's order list, words in the scratch
+};
+
+NW_HD uint64_t canon_list_words(uint64_t total) { return (total + 31) / 32 + 1; }
+
+// The state of frame [off, off + len) with scan result r; for kCanonDone, *jb is filled in.
+NW_HD uint32_t canon_begin(const uint32_t* w, uint64_t off, uint64_t len, const rec_t& r,
+                           uint64_t order_cap, canon_job_t* jb) {
+  if ((r.kind != 0 && r.kind != 2) || r.canonical) return kCanonNone;
+  const uint64_t pay = off + 12 + r.alen + 16, par = pay + 36 * (uint64_t)r.np + 8;
+  if (par + 32 * (uint64_t)r.nq + 96 > off + len) return kCanonNone;   // (not the scan's record)
+  if ((uint64_t)r.np + r.nq > kCanonMax) return kCanonOver;
+  *jb = canon_job_t{w, pay, par, r.np, r.nq, (off + 31) / 32, order_cap};
+  return kCanonDone;
+}
+
+// keys: 8 (np + nq) words.
+NW_HD void canon_stage(uint32_t lane, uint32_t lanes, const canon_job_t& jb, uint32_t* keys) {
+  const uint32_t T = 8 * (jb.np + jb.nq);
+  for (uint32_t t = lane; t < T; t += lanes) {
+    const uint32_t e = t / 8, k = t % 8;
+    const uint64_t a = e < jb.np ? jb.pay + 36 * (uint64_t)e : jb.par + 32 * (uint64_t)(e - jb.np);
+    keys[t] = bswap32(rd_u32(jb.w, a + 4 * k));
+  }
+}
+
+// -1 / 0 / 1: the staged key a against the key held in k[8].
+NW_HD int canon_cmp(const uint32_t* a, const uint32_t* k) {
+  for (int i = 0; i < 8; ++i)
+    if (a[i] != k[i]) return a[i] < k[i] ? -1 : 1;
+  return 0;
+}
+
+// kept: np + nq words, 1 = the entry survives.
+NW_HD void canon_mark(uint32_t lane, uint32_t lanes, const canon_job_t& jb, const uint32_t* keys,
+                      uint32_t* kept) {
+  const uint32_t n = jb.np + jb.nq;
+  for (uint32_t i = lane; i < n; i += lanes) {
+    const uint32_t end = i < jb.np ? jb.np : n;
+    uint32_t k[8];
+    for (int x = 0; x < 8; ++x) k[x] = keys[8 * i + x];
+    uint32_t keep = 1;
+    for (uint32_t j = i + 1; j < end && keep; ++j)
+      if (canon_cmp(keys + 8 * j, k) == 0) keep = 0;
+    kept[i] = keep;
+  }
+}
+
+// Writes the order list and *out (state kCanonDone).
+NW_HD void canon_rank(uint32_t lane, uint32_t lanes, const canon_job_t& jb, const uint32_t* keys,
+                      const uint32_t* kept, uint32_t* order, canon_t* out) {
+  const uint32_t n = jb.np + jb.nq;
+  for (uint32_t i = lane; i < n; i += lanes) {
+    if (!kept[i]) continue;
+    const uint32_t beg = i < jb.np ? 0 : jb.np, end = i < jb.np ? jb.np : n;
+    uint32_t k[8];
+    for (int x = 0; x < 8; ++x) k[x] = keys[8 * i + x];
+    uint32_t pos = 0;
+    for (uint32_t j = beg; j < end; ++j)
+      if (kept[j] && canon_cmp(keys + 8 * j, k) < 0) ++pos;
+    const uint64_t at = jb.list + beg + pos;   // beg + pos < np + nq
+    if (at < jb.cap) order[at] = i - beg;
+  }
+  // the counts: one lane per section (the same lane when there is only one)
+  if (lane == 0) {
+    uint32_t c = 0;
+    for (uint32_t j = 0; j < jb.np; ++j) c += kept[j];
+    out->np_u = c;
+    out->state = kCanonDone;
+    out->reserved = 0;
+  }
+  if (lane == (lanes > 1 ? 1u : 0u)) {
+    uint32_t c = 0;
+    for (uint32_t j = jb.np; j < n; ++j) c += kept[j];
+    out->nq_u = c;
+  }
+}
+
+// Bytes of the `Hash for Header` input of a canonicalised frame.
+NW_HD uint64_t header_len(const canon_t& c) { return 40 + 36 * (uint64_t)c.np_u + 32 * (uint64_t)c.nq_u; }
+
+// emit_lane for a frame whose canon_t says kCanonDone: the header bytes take their payload
+// entries and parents through the order list (header word t of the payload range is word
+// (t - 10) % 9 of wire entry order[(t - 10) / 9], parents likewise, 8 words each) and their
+// length and the payload count from the kept counts; the id, the signature and the votes are
+// found with the raw counts, as in emit_lane. order / order_cap: the whole scratch. An order
+// index that is not below its section's raw count writes nothing.
+NW_HD void emit_lane_canon(const uint32_t* w, uint64_t off, uint64_t len, const rec_t& r,
+                           const canon_t& c, const uint32_t* order, uint64_t order_cap,
+                           const dst_t& d, const out_t& o, uint32_t lane, uint32_t G) {
+  if (d.slot == kNoSlot) return;
+  if ((r.kind != 0 && r.kind != 2) || r.canonical || c.state != kCanonDone) return;
+  if (c.np_u > r.np || c.nq_u > r.nq) return;
+  const uint64_t list = (off + 31) / 32;
+  if (list + r.np + r.nq > order_cap) return;
+  const uint32_t* ord = order + list;
+  const int k = r.kind == 2 ? 1 : 0;
+  const uint64_t hl = header_len(c);
+  if (d.slot >= o.nitems[k] || d.hb_off > o.hb_len[k] || hl > o.hb_len[k] - d.hb_off) return;
+  if (k && ((uint64_t)d.vote0 + r.nv > o.nvotes)) return;
+  const uint64_t at = off + 12, rnd = at + r.alen, pay = rnd + 16, par = pay + 36 * (uint64_t)r.np + 8,
+                 idp = par + 32 * (uint64_t)r.nq, vts = idp + 96 + 8;
+  if (idp + 96 > off + len) return;
+  if (lane == 0) {
+    o.ho[k][d.slot] = d.hb_off;
+    o.ho[k][(uint64_t)d.slot + 1] = d.hb_off + hl;
+    o.pc[k][d.slot] = c.np_u;
+    if (k) {
+      o.vo[d.slot] = d.vote0;
+      o.vo[(uint64_t)d.slot + 1] = (uint64_t)d.vote0 + r.nv;
+    }
+  }
+  uint32_t* hb = reinterpret_cast<uint32_t*>(o.hb[k] + d.hb_off);
+  const uint32_t hw = (uint32_t)(hl / 4), pw = 10 + 9 * c.np_u;
+  const uint32_t T = hw + 24 + (k ? 24 * r.nv : 0);
+  uint32_t wv = 0;
+  uint64_t wpos = vts;
+  for (uint32_t t = lane; t < T; t += G) {
+    if (t < 8) hb[t] = b64_word(w, at, t);
+    else if (t < 10) hb[t] = rd_u32(w, rnd + 4 * (t - 8));
+    else if (t < pw) {
+      const uint32_t e = ord[(t - 10) / 9];
+      if (e < r.np) hb[t] = rd_u32(w, pay + 36 * (uint64_t)e + 4 * ((t - 10) % 9));
+    } else if (t < hw) {
+      const uint32_t e = ord[r.np + (t - pw) / 8];
+      if (e < r.nq) hb[t] = rd_u32(w, par + 32 * (uint64_t)e + 4 * ((t - pw) % 8));
+    } else if (t < hw + 8) o.ids[k][8 * (uint64_t)d.slot + (t - hw)] = rd_u32(w, idp + 4 * (t - hw));
     else if (t < hw + 24)
       o.sigs[k][16 * (uint64_t)d.slot + (t - hw - 8)] = rd_u32(w, idp + 32 + 4 * (t - hw - 8));
     else {

@@ -28,9 +28,10 @@ MSG_HEADER, MSG_VOTE, MSG_CERTIFICATE, MSG_CERTIFICATES_REQUEST = 0, 1, 2, 3
 DAG_SERIALIZATION = 21
 
 WIRE_DECODE_DEVICE = 1
+WIRE_CANON_DEVICE = 2
 
 __all__ = ["serialize", "serialize_certificates_request", "verify_primary_messages", "scan",
-           "stats", "WIRE_DECODE_DEVICE",
+           "stats", "WIRE_DECODE_DEVICE", "WIRE_CANON_DEVICE",
            "MSG_HEADER", "MSG_VOTE", "MSG_CERTIFICATE", "MSG_CERTIFICATES_REQUEST",
            "DAG_SERIALIZATION"]
 
@@ -87,10 +88,13 @@ def verify_primary_messages(committee: Committee | dict, frames: Sequence[bytes]
     Returns (kind int32[n]: MSG_* or -1, status int32[n]: 0 / NW_DAG_*, index uint64[n]).
     decode: "host" (host threads parse the frames), "device" (the frames are copied up raw
     and decoded by kernels, nw_primary_messages_verify_wire_ex with NW_WIRE_DECODE_DEVICE),
-    or None: nw_primary_messages_verify_wire's default (host, unless NW_WIRE_DECODE=device is
-    set in the environment). The results are identical."""
-    if decode not in (None, "host", "device"):
-        raise ValueError(f"decode must be 'host' or 'device', not {decode!r}")
+    "device-canon" (NW_WIRE_DECODE_DEVICE | NW_WIRE_CANON_DEVICE: the device also sorts and
+    de-duplicates frames whose payload or parents arrive out of order, which "device" hands
+    back to the host), or None: nw_primary_messages_verify_wire's default (host, unless
+    NW_WIRE_DECODE=device or device-canon is set in the environment). The results are
+    identical."""
+    if decode not in (None, "host", "device", "device-canon"):
+        raise ValueError(f"decode must be 'host', 'device' or 'device-canon', not {decode!r}")
     data, offs = frames if isinstance(frames, tuple) else frames_soa(frames)
     n = len(offs) - 1
     kind = np.zeros(max(n, 1), np.int32)
@@ -102,7 +106,8 @@ def verify_primary_messages(committee: Committee | dict, frames: Sequence[bytes]
                                                          _p(kind), _p(st), _p(ix)),
               "nw_primary_messages_verify_wire")
     else:
-        flags = WIRE_DECODE_DEVICE if decode == "device" else 0
+        flags = {"host": 0, "device": WIRE_DECODE_DEVICE,
+                 "device-canon": WIRE_DECODE_DEVICE | WIRE_CANON_DEVICE}[decode]
         check(_lib.lib().nw_primary_messages_verify_wire_ex(ctypes.byref(cc), _p(data), _p(offs),
                                                             n, flags, _p(kind), _p(st), _p(ix)),
               "nw_primary_messages_verify_wire_ex")
