@@ -61,15 +61,16 @@ hostcheck: tools/libnw_hostcheck.so
 tools/libnw_hostcheck.so: tools/hostcheck.hip $(HDRS)
 	$(HIPCC) --cuda-host-only -O2 -std=c++17 -fPIC -shared -Iinclude $< -o $@
 
-# the device wire decoder (nw_wiredec.hpp) compiled for the CPU (tests/test_wire_device_cpu.py)
+# the device wire decoder (nw_wiredec.hpp) and the host placement (nw_wireplace.hpp) compiled for
+# the CPU (tests/test_wire_device_cpu.py, test_wire_canon_cpu.py, test_wire_place_cpu.py)
 wirecheck: tools/libnw_wirecheck.so
-tools/libnw_wirecheck.so: tools/wirecheck.hip $(CSRC)/nw_wiredec.hpp
+tools/libnw_wirecheck.so: tools/wirecheck.hip tools/wire_single.hpp $(CSRC)/nw_wiredec.hpp $(CSRC)/nw_wireplace.hpp
 	$(HIPCC) --cuda-host-only -O2 -std=c++17 -fPIC -shared -Iinclude $< -o $@
 
 # the same decoder text under AddressSanitizer / UBSan over generated and mutated frames, as a
 # stand-alone CPU program (not part of `all`): make wiresan && tools/wire_canon_san
 wiresan: tools/wire_canon_san
-tools/wire_canon_san: tools/wire_canon_san.cpp $(CSRC)/nw_wiredec.hpp
+tools/wire_canon_san: tools/wire_canon_san.cpp tools/wire_single.hpp $(CSRC)/nw_wiredec.hpp
 	g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all $< -o $@
 
 loadgen: tools/libnw_loadgen.so

@@ -38,7 +38,7 @@
 #include "narwhal_amd.h"
 #include "nw_kernels.h"
 #include "nw_runtime.h"
-#include "nw_wiredec.hpp"
+#include "nw_wireplace.hpp"
 
 struct nw_job {
   int dev = -1;
@@ -1326,9 +1326,9 @@ bool wire_stamps() {   // NW_WIRE_STAMPS=1: per-phase host times of every device
 //      H2D through the job's pinned buffer;
 //   2. k_wire_scan writes one record per frame; the records come back and the stream is
 //      synchronised, the only wait before the verdicts;
-//   3. the host's prefix sums over the records place every frame (slot within its kind,
-//      header byte offset, first vote) and give cert_pipeline the host_vote_offsets it plans
-//      with; the destinations go up and k_wire_emit writes the structure-of-arrays;
+//   3. the host's prefix sums over the records (wd::place) place every frame (slot within
+//      its kind, header byte offset, first vote) and give cert_pipeline the host_vote_offsets
+//      it plans with; the destinations go up and k_wire_emit writes the structure-of-arrays;
 //   4. cert_pipeline (headers), cert_pipeline (certificates) and votes_pipeline run on the
 //      job's stream over those arrays, sharing one workspace (stream order);
 //   5. the per-kind statuses and indices come back and are scattered into frame order.
@@ -1460,84 +1460,40 @@ int nw::rt::wire_verify_device(int dev, const nw_committee* com, const uint8_t* 
   const wd::rec_t* rec = reinterpret_cast<const wd::rec_t*>(H + o_rec);
   const wd::canon_t* can = canon ? reinterpret_cast<const wd::canon_t*>(H + o_can) : nullptr;
   wd::dst_t* dst = reinterpret_cast<wd::dst_t*>(H + o_dst);
-  uint64_t cnt[2] = {0, 0}, hbl[2] = {0, 0}, nvm = 0, nvotes = 0, ncanon = 0;
+  wd::place_t pl;
   thread_local std::vector<uint64_t> cvo;
-  cvo.assign(1, 0);
-  const char* bad = nullptr;
-  for (size_t i = 0; i < n && !bad; ++i) {
-    const wd::rec_t& r = rec[i];
-    const uint64_t len = ho[i + 1] - ho[i];
-    dst[i] = wd::dst_t{0, wd::kNoSlot, 0};
-    const bool noncanon = (r.kind == 0 || r.kind == 2) && !r.canonical;
-    if (r.kind == wd::kOverCap || (noncanon && (!canon || can[i].state == wd::kCanonOver))) {
-      host_frames->push_back(i);
-      continue;
-    }
-    kind_out[i] = r.kind;
-    status_out[i] = r.kind < 0 ? NW_DAG_SERIALIZATION : 0;
-    if (index_out) index_out[i] = 0;
-    if (r.kind == -1 || r.kind == NW_MSG_CERTIFICATES_REQUEST) continue;
-    if (r.kind == NW_MSG_VOTE) {
-      if (124 + (uint64_t)r.alen + r.vlen > len) bad = "vote record";   // 4 + 32 + 8 + 2 keys + 64
-      dst[i].slot = (uint32_t)nvm++;
-      continue;
-    }
-    if (r.kind != NW_MSG_HEADER && r.kind != NW_MSG_CERTIFICATE) {
-      bad = "record kind";
-      break;
-    }
-    const int k = r.kind == NW_MSG_CERTIFICATE;
-    uint64_t hl = wd::header_len(r);
-    if (noncanon) {   // the kept counts: at most the raw ones, and none only where none was sent
-      const wd::canon_t& c = can[i];
-      if (c.state != wd::kCanonDone || c.np_u > r.np || c.nq_u > r.nq || (r.np && !c.np_u) ||
-          (r.nq && !c.nq_u))
-        bad = "canon record";
-      hl = wd::header_len(c);
-      ++ncanon;
-    }
-    // what the frame itself holds: 4 + 8 + key + 8 + 8 + payload + 8 + parents + 96 (+ 8 + votes)
-    if (132 + (uint64_t)r.alen + 36 * (uint64_t)r.np + 32 * (uint64_t)r.nq +
-            (k ? 8 + 72 * (uint64_t)r.nv : 0) > len)
-      bad = "header record";
-    dst[i] = wd::dst_t{hbl[k], (uint32_t)cnt[k]++, (uint32_t)nvotes};
-    hbl[k] += hl;
-    if (k) {
-      nvotes += r.nv;
-      cvo.push_back(nvotes);
-    }
-  }
-  if (!bad && (hbl[0] + hbl[1] > total || nvotes > vbound)) bad = "record totals";
+  const char* bad = wd::place(rec, can, ho, n, total, vbound, dst, &pl, &cvo, host_frames,
+                              kind_out, status_out, index_out);
   if (bad) return job_abort(j, set_err(NW_E_DEVICE, bad));
-  const uint64_t nh = cnt[0], nc = cnt[1];
+  const uint64_t nh = pl.cnt[0], nc = pl.cnt[1];
   Packer S;
   S.off = o_soa;
   wd::out_t out{};
   for (int k = 0; k < 2; ++k) {
-    out.hb[k] = reinterpret_cast<uint8_t*>(D + S.add(hbl[k]));
-    out.hb_len[k] = hbl[k];
-    out.ho[k] = reinterpret_cast<uint64_t*>(D + S.add(8 * (cnt[k] + 1)));
-    out.pc[k] = reinterpret_cast<uint32_t*>(D + S.add(4 * cnt[k]));
-    out.ids[k] = reinterpret_cast<uint32_t*>(D + S.add(32 * cnt[k]));
-    out.sigs[k] = reinterpret_cast<uint32_t*>(D + S.add(64 * cnt[k]));
-    out.nitems[k] = (uint32_t)cnt[k];
+    out.hb[k] = reinterpret_cast<uint8_t*>(D + S.add(pl.hbl[k]));
+    out.hb_len[k] = pl.hbl[k];
+    out.ho[k] = reinterpret_cast<uint64_t*>(D + S.add(8 * (pl.cnt[k] + 1)));
+    out.pc[k] = reinterpret_cast<uint32_t*>(D + S.add(4 * pl.cnt[k]));
+    out.ids[k] = reinterpret_cast<uint32_t*>(D + S.add(32 * pl.cnt[k]));
+    out.sigs[k] = reinterpret_cast<uint32_t*>(D + S.add(64 * pl.cnt[k]));
+    out.nitems[k] = (uint32_t)pl.cnt[k];
   }
   out.vo = reinterpret_cast<uint64_t*>(D + S.add(8 * (nc + 1)));
-  out.vpk = reinterpret_cast<uint32_t*>(D + S.add(32 * nvotes));
-  out.vsig = reinterpret_cast<uint32_t*>(D + S.add(64 * nvotes));
-  out.nvotes = (uint32_t)nvotes;
-  out.v_ids = reinterpret_cast<uint32_t*>(D + S.add(32 * nvm));
-  out.v_rounds = reinterpret_cast<uint64_t*>(D + S.add(8 * nvm));
-  out.v_origins = reinterpret_cast<uint32_t*>(D + S.add(32 * nvm));
-  out.v_authors = reinterpret_cast<uint32_t*>(D + S.add(32 * nvm));
-  out.v_sigs = reinterpret_cast<uint32_t*>(D + S.add(64 * nvm));
-  out.nvmsg = (uint32_t)nvm;
+  out.vpk = reinterpret_cast<uint32_t*>(D + S.add(32 * pl.nvotes));
+  out.vsig = reinterpret_cast<uint32_t*>(D + S.add(64 * pl.nvotes));
+  out.nvotes = (uint32_t)pl.nvotes;
+  out.v_ids = reinterpret_cast<uint32_t*>(D + S.add(32 * pl.nvm));
+  out.v_rounds = reinterpret_cast<uint64_t*>(D + S.add(8 * pl.nvm));
+  out.v_origins = reinterpret_cast<uint32_t*>(D + S.add(32 * pl.nvm));
+  out.v_authors = reinterpret_cast<uint32_t*>(D + S.add(32 * pl.nvm));
+  out.v_sigs = reinterpret_cast<uint32_t*>(D + S.add(64 * pl.nvm));
+  out.nvmsg = (uint32_t)pl.nvm;
   const size_t ws_need = std::max({nw::rt::cert_workspace_bytes(nh, 0),
-                                   nw::rt::cert_workspace_bytes(nc, nvotes),
-                                   nw::rt::votes_workspace_bytes(nvm)});
+                                   nw::rt::cert_workspace_bytes(nc, pl.nvotes),
+                                   nw::rt::votes_workspace_bytes(pl.nvm)});
   if (S.off > o_ws || o_ws + ws_need > j->dcap)
     return job_abort(j, set_err(NW_E_OUT_OF_MEMORY, "wire job buffer bound"));
-  const uint64_t nitems = nh + nc + nvm;
+  const uint64_t nitems = nh + nc + pl.nvm;
   if (nitems) {
     e = hipMemcpyAsync(D + o_dst, H + o_dst, sizeof(wd::dst_t) * n, hipMemcpyHostToDevice,
                        j->stream);
@@ -1550,27 +1506,27 @@ int nw::rt::wire_verify_device(int dev, const nw_committee* com, const uint8_t* 
     int32_t* dst_st = reinterpret_cast<int32_t*>(D + o_st);
     uint64_t* dst_ix = reinterpret_cast<uint64_t*>(D + o_ix);
     for (int k = 0; k < 2 && !rc; ++k) {
-      if (!cnt[k]) continue;
+      if (!pl.cnt[k]) continue;
       nw_certificates d{};
-      d.n = cnt[k];
+      d.n = pl.cnt[k];
       d.header_bytes = out.hb[k];
       d.header_offsets = out.ho[k];
       d.payload_counts = out.pc[k];
       d.ids = reinterpret_cast<const uint8_t*>(out.ids[k]);
       d.header_sigs = reinterpret_cast<const uint8_t*>(out.sigs[k]);
-      d.header_bytes_len = hbl[k];
+      d.header_bytes_len = pl.hbl[k];
       if (k) {
         d.vote_offsets = out.vo;
         d.vote_pks = reinterpret_cast<const uint8_t*>(out.vpk);
         d.vote_sigs = reinterpret_cast<const uint8_t*>(out.vsig);
-        d.nvotes = nvotes;
+        d.nvotes = pl.nvotes;
       }
       rc = nw::rt::cert_pipeline(dev, dcom, d, k ? cvo.data() : nullptr, !k, nullptr, nullptr,
                                  D + o_ws, dst_st + (k ? nh : 0), dst_ix + (k ? nh : 0),
                                  j->stream, ctag, nullptr, com->pks);
     }
-    if (!rc && nvm)
-      rc = nw::rt::votes_pipeline(dev, dcom, nvm, reinterpret_cast<const uint8_t*>(out.v_ids),
+    if (!rc && pl.nvm)
+      rc = nw::rt::votes_pipeline(dev, dcom, pl.nvm, reinterpret_cast<const uint8_t*>(out.v_ids),
                                   out.v_rounds, reinterpret_cast<const uint8_t*>(out.v_origins),
                                   reinterpret_cast<const uint8_t*>(out.v_authors),
                                   reinterpret_cast<const uint8_t*>(out.v_sigs), D + o_ws,
@@ -1601,7 +1557,7 @@ int nw::rt::wire_verify_device(int dev, const nw_committee* com, const uint8_t* 
             "wait %.0f us, place+emit+checks %.0f us (headers %llu certs %llu votes %llu "
             "vote msgs %llu canonicalised %llu host %zu)\n", n, (unsigned long long)total,
             us(t0, t1), us(t1, t2), us(t2, t3), (unsigned long long)nh, (unsigned long long)nc,
-            (unsigned long long)nvotes, (unsigned long long)nvm, (unsigned long long)ncanon,
+            (unsigned long long)pl.nvotes, (unsigned long long)pl.nvm, (unsigned long long)pl.ncanon,
             host_frames->size());
   }
   job_recycle(j);

@@ -14,9 +14,9 @@
 //                 then 24 words per vote: 8 decoded key words and 16 signature words), lane l
 //                 takes tasks l, l + G, ...; contiguous lanes write contiguous words. Where
 //                 each frame's rows go (its slot, header byte offset, first vote) comes from
-//                 the host's prefix sums over the scan's records; the counts that drive the
-//                 writes are the scan's own records in device memory, and every write is
-//                 checked against the arrays' capacities.
+//                 the host's prefix sums over the scan's records (nw_wireplace.hpp); the
+//                 counts that drive the writes are the scan's own records in device memory,
+//                 and every write is checked against the arrays' capacities.
 //   k_wire_canon  (NW_WIRE_CANON_DEVICE) one workgroup per frame, between the scan and the
 //                 read-back of its records: a Header / Certificate frame whose payload keys
 //                 or parents are not strictly increasing gets the BTreeMap / BTreeSet sort
@@ -25,7 +25,7 @@
 //                 every other frame's workgroup writes "not applicable" and exits. 64 or
 //                 256 lanes per workgroup (the host picks by mean frame size: the walks
 //                 are O(entries^2 / lanes)). k_wire_emit then reads such a frame through
-//                 its order list (emit_lane_canon).
+//                 its order list (emit_lane<true>).
 //
 // These kernels move bytes: a few hundred to a few thousand per frame, no arithmetic beyond
 // base64 (and, in k_wire_canon, key compares). The verification kernels that follow dominate
@@ -73,12 +73,8 @@ __global__ __launch_bounds__(256) void k_wire_emit(const uint32_t* __restrict__ 
   const uint64_t off = offsets[i], end = offsets[i + 1];
   if (end < off || end > total_bytes) return;
   const wd::rec_t r = recs[i];
-  if (kCanon && (r.kind == 0 || r.kind == 2) && !r.canonical) {
-    wd::emit_lane_canon(frames, off, end - off, r, cans[i], order, order_cap, d, out,
-                        (uint32_t)(t % G), G);
-    return;
-  }
-  wd::emit_lane(frames, off, end - off, r, d, out, (uint32_t)(t % G), G);
+  wd::emit_lane<kCanon>(frames, off, end - off, r, kCanon ? cans + i : nullptr, order,
+                        order_cap, d, out, (uint32_t)(t % G), G);
 }
 
 // One workgroup of L lanes per frame. Every branch before a barrier depends on the frame

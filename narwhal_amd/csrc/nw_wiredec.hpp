@@ -14,12 +14,14 @@
 //         no sort is needed. Non-canonical Header / Certificate frames (which an honest
 //         sender never produces: bincode writes a BTreeMap / BTreeSet in key order) are left
 //         to the host decoder, unless the caller asks for the canonicalisation below
-//         (canon_*, emit_lane_canon), which sorts and de-duplicates them on the device.
+//         (canon_*, emit_lane<true>), which sorts and de-duplicates them on the device.
 //   emit  writes the item's structure-of-arrays rows as 4-byte words, cooperatively: the
 //         frame's output is a list of word tasks, lane l of a group of G takes tasks l,
 //         l + G, ..., so contiguous lanes write contiguous words. Every destination is
 //         4-byte aligned (header bytes are 40 + 36 np + 32 nq long, every other row is a
-//         multiple of 32 bytes).
+//         multiple of 32 bytes). A record that does not fit its own frame (header_layout /
+//         vote_layout) emits nothing, a certificate record whose votes do not fit (8 + 72 nv)
+//         not even its header rows; the host rejects such a record before any emit runs.
 //
 // Memory access: frames start at arbitrary byte offsets, so the frame buffer is read as
 // aligned 32-bit words plus a shift (never an unaligned wide load). The buffer `w` must be
@@ -277,90 +279,32 @@ NW_HD rec_t scan(const uint32_t* w, uint64_t off, uint64_t len) {
   return r;
 }
 
-// Bytes of the `Hash for Header` input of a scanned header / certificate.
-NW_HD uint64_t header_len(const rec_t& r) { return 40 + 36 * (uint64_t)r.np + 32 * (uint64_t)r.nq; }
-
-// ---- emit ---------------------------------------------------------------------------
-// Lane `lane` of `G` of the emit of one frame (r = its scan result, d = its destination).
-// Only for a canonical Header / Certificate frame or a Vote frame with a slot; every write
-// is checked against o's capacities, so a record and a destination that disagree write
-// nothing out of bounds.
-NW_HD void emit_lane(const uint32_t* w, uint64_t off, uint64_t len, const rec_t& r,
-                     const dst_t& d, const out_t& o, uint32_t lane, uint32_t G) {
-  if (d.slot == kNoSlot) return;
-  if (r.kind == 1) {
-    if (d.slot >= o.nvmsg) return;
-    // id 4 | round 36 | origin: len 44, text 52 | author: len, text | signature
-    const uint64_t ot = off + 52, at = ot + r.alen + 8, sg = at + r.vlen;
-    if (sg + 64 > off + len) return;
-    for (uint32_t t = lane; t < 42; t += G) {
-      if (t < 8) o.v_ids[8 * (uint64_t)d.slot + t] = rd_u32(w, off + 4 + 4 * t);
-      else if (t < 10)
-        reinterpret_cast<uint32_t*>(o.v_rounds)[2 * (uint64_t)d.slot + (t - 8)] =
-            rd_u32(w, off + 36 + 4 * (t - 8));
-      else if (t < 18) o.v_origins[8 * (uint64_t)d.slot + (t - 10)] = b64_word(w, ot, t - 10);
-      else if (t < 26) o.v_authors[8 * (uint64_t)d.slot + (t - 18)] = b64_word(w, at, t - 18);
-      else o.v_sigs[16 * (uint64_t)d.slot + (t - 26)] = rd_u32(w, sg + 4 * (t - 26));
-    }
-    return;
-  }
-  if ((r.kind != 0 && r.kind != 2) || !r.canonical) return;
-  const int k = r.kind == 2 ? 1 : 0;
-  const uint64_t hl = header_len(r);
-  if (d.slot >= o.nitems[k] || d.hb_off > o.hb_len[k] || hl > o.hb_len[k] - d.hb_off) return;
-  if (k && ((uint64_t)d.vote0 + r.nv > o.nvotes)) return;
-  // variant 0 | author: len 4, text 12 | round | np | payload | nq | parents | id | sig |
-  // (certificate) nv | votes: len, text, signature 64
-  const uint64_t at = off + 12, rnd = at + r.alen, pay = rnd + 16, par = pay + 36 * (uint64_t)r.np + 8,
-                 idp = par + 32 * (uint64_t)r.nq, vts = idp + 96 + 8;
-  if (idp + 96 > off + len) return;
-  if (lane == 0) {
-    o.ho[k][d.slot] = d.hb_off;
-    o.ho[k][(uint64_t)d.slot + 1] = d.hb_off + hl;   // the next frame writes the same value
-    o.pc[k][d.slot] = r.np;
-    if (k) {
-      o.vo[d.slot] = d.vote0;
-      o.vo[(uint64_t)d.slot + 1] = (uint64_t)d.vote0 + r.nv;
-    }
-  }
-  uint32_t* hb = reinterpret_cast<uint32_t*>(o.hb[k] + d.hb_off);
-  const uint32_t hw = (uint32_t)(hl / 4), pw = 10 + 9 * r.np;
-  const uint32_t T = hw + 24 + (k ? 24 * r.nv : 0);
-  // votes with differing key text lengths: this lane walks forward from vote to vote
-  uint32_t wv = 0;
-  uint64_t wpos = vts;
-  for (uint32_t t = lane; t < T; t += G) {
-    if (t < 8) hb[t] = b64_word(w, at, t);
-    else if (t < 10) hb[t] = rd_u32(w, rnd + 4 * (t - 8));
-    else if (t < pw) hb[t] = rd_u32(w, pay + 4 * (uint64_t)(t - 10));
-    else if (t < hw) hb[t] = rd_u32(w, par + 4 * (uint64_t)(t - pw));
-    else if (t < hw + 8) o.ids[k][8 * (uint64_t)d.slot + (t - hw)] = rd_u32(w, idp + 4 * (t - hw));
-    else if (t < hw + 24)
-      o.sigs[k][16 * (uint64_t)d.slot + (t - hw - 8)] = rd_u32(w, idp + 32 + 4 * (t - hw - 8));
-    else {
-      const uint32_t v = (t - hw - 24) / 24, j = (t - hw - 24) % 24;
-      uint64_t vp, L;
-      if (r.vlen) {
-        L = r.vlen;
-        vp = vts + (uint64_t)v * (8 + L + 64);
-      } else {
-        for (; wv < v; ++wv) {
-          if (wpos + 8 > off + len) return;
-          const uint64_t l = rd_u64(w, wpos);
-          if (l > len) return;
-          wpos += 8 + l + 64;
-        }
-        if (wpos + 8 > off + len) return;
-        vp = wpos;
-        L = rd_u64(w, vp);
-      }
-      if (L > len || vp + 8 + L + 64 > off + len) return;
-      const uint64_t vs = (uint64_t)d.vote0 + v;
-      if (j < 8) o.vpk[8 * vs + j] = b64_word(w, vp + 8, j);
-      else o.vsig[16 * vs + (j - 8)] = rd_u32(w, vp + 8 + L + 4 * (j - 8));
-    }
-  }
+// ---- frame layout -------------------------------------------------------------------
+// The only place that knows the field offsets: where a record says its frame's fields are
+// (absolute byte addresses) and whether it fits its own frame [off, off + len) (ok). The emit,
+// canon_begin and the host's placement (nw_wireplace.hpp) ask here. Sums in 64 bits: no wrap.
+// variant 4 | author: len 8, text | round 8 | np 8 | payload 36 each | nq 8 | parents 32 each
+// | id 32 | signature 64 | (certificate) nv 8 | votes: len 8, text, signature 64
+struct hdr_layout_t {   // author text, round, payload, parents, id, end of the signature, votes
+  uint64_t at, rnd, pay, par, idp, hend, vts; bool ok;
+};
+NW_HD hdr_layout_t header_layout(uint64_t off, uint64_t len, const rec_t& r) {
+  const uint64_t pb = 36 * (uint64_t)r.np, qb = 32 * (uint64_t)r.nq, at = off + 12,
+                 rnd = at + r.alen, pay = rnd + 16, par = pay + pb + 8, idp = par + qb;
+  return {at, rnd, pay, par, idp, idp + 96, idp + 96 + 8,
+          132 + (uint64_t)r.alen + pb + qb + (r.kind == 2 ? 8 + 72 * (uint64_t)r.nv : 0) <= len};
 }
+// variant 4 | id 32 | round 8 | origin: len 8, text | author: len 8, text | signature 64
+struct vote_layout_t {   // id, round, origin text, author text, signature; the record fits
+  uint64_t id, rnd, ot, at, sg; bool ok;
+};
+NW_HD vote_layout_t vote_layout(uint64_t off, uint64_t len, const rec_t& r) {
+  const uint64_t ot = off + 52, at = ot + r.alen + 8;
+  return {off + 4, off + 36, ot, at, at + r.vlen, 124 + (uint64_t)r.alen + r.vlen <= len};
+}
+
+// Bytes of the `Hash for Header` input (np, nq: raw counts, or a canonicalised frame's kept ones).
+NW_HD uint64_t header_len(uint32_t np, uint32_t nq) { return 40 + 36 * (uint64_t)np + 32 * (uint64_t)nq; }
 
 // ---- canonicalisation of non-canonical Header / Certificate frames --------------------
 // BTreeMap / BTreeSet deserialisation of a frame whose payload keys or parents are not
@@ -414,10 +358,14 @@ NW_HD uint64_t canon_list_words(uint64_t total) { return (total + 31) / 32 + 1; 
 NW_HD uint32_t canon_begin(const uint32_t* w, uint64_t off, uint64_t len, const rec_t& r,
                            uint64_t order_cap, canon_job_t* jb) {
   if ((r.kind != 0 && r.kind != 2) || r.canonical) return kCanonNone;
-  const uint64_t pay = off + 12 + r.alen + 16, par = pay + 36 * (uint64_t)r.np + 8;
-  if (par + 32 * (uint64_t)r.nq + 96 > off + len) return kCanonNone;   // (not the scan's record)
+  // Deliberately h.hend, not h.ok: only the part this reads, up to the signature, as before
+  // the layout functions. With the votes' term the kernel's loops land elsewhere, which cost
+  // k_wire_canon<256> 3 to 8 % on frames of 1,018 entries (profiles/wire03; it may differ with
+  // another compiler). The placement rejects a record whose votes do not fit.
+  const hdr_layout_t h = header_layout(off, len, r);
+  if (h.hend > off + len) return kCanonNone;   // (not the scan's record)
   if ((uint64_t)r.np + r.nq > kCanonMax) return kCanonOver;
-  *jb = canon_job_t{w, pay, par, r.np, r.nq, (off + 31) / 32, order_cap};
+  *jb = canon_job_t{w, h.pay, h.par, r.np, r.nq, (off + 31) / 32, order_cap};
   return kCanonDone;
 }
 
@@ -483,63 +431,66 @@ NW_HD void canon_rank(uint32_t lane, uint32_t lanes, const canon_job_t& jb, cons
   }
 }
 
-// Bytes of the `Hash for Header` input of a canonicalised frame.
-NW_HD uint64_t header_len(const canon_t& c) { return 40 + 36 * (uint64_t)c.np_u + 32 * (uint64_t)c.nq_u; }
-
-// emit_lane for a frame whose canon_t says kCanonDone: the header bytes take their payload
-// entries and parents through the order list (header word t of the payload range is word
-// (t - 10) % 9 of wire entry order[(t - 10) / 9], parents likewise, 8 words each) and their
-// length and the payload count from the kept counts; the id, the signature and the votes are
-// found with the raw counts, as in emit_lane. order / order_cap: the whole scratch. An order
-// index that is not below its section's raw count writes nothing.
-NW_HD void emit_lane_canon(const uint32_t* w, uint64_t off, uint64_t len, const rec_t& r,
-                           const canon_t& c, const uint32_t* order, uint64_t order_cap,
-                           const dst_t& d, const out_t& o, uint32_t lane, uint32_t G) {
-  if (d.slot == kNoSlot) return;
-  if ((r.kind != 0 && r.kind != 2) || r.canonical || c.state != kCanonDone) return;
-  if (c.np_u > r.np || c.nq_u > r.nq) return;
+// ---- emit ---------------------------------------------------------------------------
+// The Header / Certificate rows of emit_lane. kSorted: the frame's canon_t c says kCanonDone,
+// and its header bytes take their payload entries and parents through the order list (header
+// word t of the payload range is word (t - 10) % 9 of wire entry order[(t - 10) / 9], parents
+// likewise, 8 words each; an index not below its section's raw count writes nothing) and
+// their length and payload count from the kept counts; the id, the signature and the votes
+// are found with the raw counts. An instance per value, so that no word pays for the choice.
+template <bool kSorted>
+NW_HD void emit_header(const uint32_t* w, uint64_t off, uint64_t len, const rec_t& r,
+                       const canon_t* c, const uint32_t* order, uint64_t order_cap,
+                       const dst_t& d, const out_t& o, uint32_t lane, uint32_t G) {
   const uint64_t list = (off + 31) / 32;
-  if (list + r.np + r.nq > order_cap) return;
-  const uint32_t* ord = order + list;
+  if (kSorted && (c->state != kCanonDone || c->np_u > r.np || c->nq_u > r.nq ||
+                  list + r.np + r.nq > order_cap))
+    return;
+  const uint32_t* ord = kSorted ? order + list : nullptr;
+  const uint32_t np = kSorted ? c->np_u : r.np, nq = kSorted ? c->nq_u : r.nq;   // of the header bytes
   const int k = r.kind == 2 ? 1 : 0;
-  const uint64_t hl = header_len(c);
+  const uint64_t hl = header_len(np, nq);
   if (d.slot >= o.nitems[k] || d.hb_off > o.hb_len[k] || hl > o.hb_len[k] - d.hb_off) return;
   if (k && ((uint64_t)d.vote0 + r.nv > o.nvotes)) return;
-  const uint64_t at = off + 12, rnd = at + r.alen, pay = rnd + 16, par = pay + 36 * (uint64_t)r.np + 8,
-                 idp = par + 32 * (uint64_t)r.nq, vts = idp + 96 + 8;
-  if (idp + 96 > off + len) return;
+  const hdr_layout_t f = header_layout(off, len, r);
+  if (!f.ok) return;
   if (lane == 0) {
     o.ho[k][d.slot] = d.hb_off;
-    o.ho[k][(uint64_t)d.slot + 1] = d.hb_off + hl;
-    o.pc[k][d.slot] = c.np_u;
+    o.ho[k][(uint64_t)d.slot + 1] = d.hb_off + hl;   // the next frame writes the same value
+    o.pc[k][d.slot] = np;
     if (k) {
       o.vo[d.slot] = d.vote0;
       o.vo[(uint64_t)d.slot + 1] = (uint64_t)d.vote0 + r.nv;
     }
   }
   uint32_t* hb = reinterpret_cast<uint32_t*>(o.hb[k] + d.hb_off);
-  const uint32_t hw = (uint32_t)(hl / 4), pw = 10 + 9 * c.np_u;
+  const uint32_t hw = (uint32_t)(hl / 4), pw = 10 + 9 * np;
   const uint32_t T = hw + 24 + (k ? 24 * r.nv : 0);
+  // votes with differing key text lengths: this lane walks forward from vote to vote
   uint32_t wv = 0;
-  uint64_t wpos = vts;
+  uint64_t wpos = f.vts;
   for (uint32_t t = lane; t < T; t += G) {
-    if (t < 8) hb[t] = b64_word(w, at, t);
-    else if (t < 10) hb[t] = rd_u32(w, rnd + 4 * (t - 8));
+    if (t < 8) hb[t] = b64_word(w, f.at, t);
+    else if (t < 10) hb[t] = rd_u32(w, f.rnd + 4 * (t - 8));
     else if (t < pw) {
-      const uint32_t e = ord[(t - 10) / 9];
-      if (e < r.np) hb[t] = rd_u32(w, pay + 36 * (uint64_t)e + 4 * ((t - 10) % 9));
+      if (kSorted) {
+        const uint32_t e = ord[(t - 10) / 9];
+        if (e < r.np) hb[t] = rd_u32(w, f.pay + 36 * (uint64_t)e + 4 * ((t - 10) % 9));
+      } else hb[t] = rd_u32(w, f.pay + 4 * (uint64_t)(t - 10));
     } else if (t < hw) {
-      const uint32_t e = ord[r.np + (t - pw) / 8];
-      if (e < r.nq) hb[t] = rd_u32(w, par + 32 * (uint64_t)e + 4 * ((t - pw) % 8));
-    } else if (t < hw + 8) o.ids[k][8 * (uint64_t)d.slot + (t - hw)] = rd_u32(w, idp + 4 * (t - hw));
+      if (kSorted) {
+        const uint32_t e = ord[r.np + (t - pw) / 8];
+        if (e < r.nq) hb[t] = rd_u32(w, f.par + 32 * (uint64_t)e + 4 * ((t - pw) % 8));
+      } else hb[t] = rd_u32(w, f.par + 4 * (uint64_t)(t - pw));
+    } else if (t < hw + 8) o.ids[k][8 * (uint64_t)d.slot + (t - hw)] = rd_u32(w, f.idp + 4 * (t - hw));
     else if (t < hw + 24)
-      o.sigs[k][16 * (uint64_t)d.slot + (t - hw - 8)] = rd_u32(w, idp + 32 + 4 * (t - hw - 8));
+      o.sigs[k][16 * (uint64_t)d.slot + (t - hw - 8)] = rd_u32(w, f.idp + 32 + 4 * (t - hw - 8));
     else {
       const uint32_t v = (t - hw - 24) / 24, j = (t - hw - 24) % 24;
       uint64_t vp, L;
       if (r.vlen) {
         L = r.vlen;
-        vp = vts + (uint64_t)v * (8 + L + 64);
+        vp = f.vts + (uint64_t)v * (8 + L + 64);
       } else {
         for (; wv < v; ++wv) {
           if (wpos + 8 > off + len) return;
@@ -557,6 +508,34 @@ NW_HD void emit_lane_canon(const uint32_t* w, uint64_t off, uint64_t len, const 
       else o.vsig[16 * vs + (j - 8)] = rd_u32(w, vp + 8 + L + 4 * (j - 8));
     }
   }
+}
+
+// Lane `lane` of `G` of the emit of one frame (r = its scan result, d = its destination): a
+// Vote frame, or a Header / Certificate frame with a slot. Every write is checked against
+// o's capacities, so a record and a destination that disagree write nothing out of bounds.
+// kCanon = false: canonical frames only; c and order are never touched.
+template <bool kCanon>
+NW_HD void emit_lane(const uint32_t* w, uint64_t off, uint64_t len, const rec_t& r,
+                     const canon_t* c, const uint32_t* order, uint64_t order_cap,
+                     const dst_t& d, const out_t& o, uint32_t lane, uint32_t G) {
+  if (d.slot == kNoSlot) return;
+  if (r.kind == 1) {
+    const vote_layout_t f = vote_layout(off, len, r);
+    if (d.slot >= o.nvmsg || !f.ok) return;
+    for (uint32_t t = lane; t < 42; t += G) {
+      if (t < 8) o.v_ids[8 * (uint64_t)d.slot + t] = rd_u32(w, f.id + 4 * t);
+      else if (t < 10)
+        reinterpret_cast<uint32_t*>(o.v_rounds)[2 * (uint64_t)d.slot + (t - 8)] =
+            rd_u32(w, f.rnd + 4 * (t - 8));
+      else if (t < 18) o.v_origins[8 * (uint64_t)d.slot + (t - 10)] = b64_word(w, f.ot, t - 10);
+      else if (t < 26) o.v_authors[8 * (uint64_t)d.slot + (t - 18)] = b64_word(w, f.at, t - 18);
+      else o.v_sigs[16 * (uint64_t)d.slot + (t - 26)] = rd_u32(w, f.sg + 4 * (t - 26));
+    }
+    return;
+  }
+  if (r.kind != 0 && r.kind != 2) return;
+  if (r.canonical) emit_header<false>(w, off, len, r, c, order, order_cap, d, o, lane, G);
+  else if (kCanon) emit_header<true>(w, off, len, r, c, order, order_cap, d, o, lane, G);
 }
 
 }  // namespace wd

@@ -1,5 +1,5 @@
 """The device canonicalisation of non-canonical Header / Certificate frames
-(narwhal_amd/csrc/nw_wiredec.hpp: canon_stage / canon_mark / canon_rank and emit_lane_canon,
+(narwhal_amd/csrc/nw_wiredec.hpp: canon_stage / canon_mark / canon_rank and emit_lane<true>,
 the text k_wire_canon and k_wire_emit run), compiled as host code into
 tools/libnw_wirecheck.so, against the Python restatement of the wire format
 (tests/test_wire.py, ref_decode: BTreeMap / BTreeSet re-sort, last value wins). Every case runs

@@ -1,6 +1,6 @@
 // wire_canon_san.cpp — TEST INFRASTRUCTURE. A stand-alone host program that runs the device
 // wire decoder's text (narwhal_amd/csrc/nw_wiredec.hpp, compiled as host code: scan,
-// canon_stage / canon_mark / canon_rank, emit_lane, emit_lane_canon) over generated frames
+// canon_stage / canon_mark / canon_rank, both instances of emit_lane) over generated frames
 // and random mutations of them, with every buffer allocated at exactly the size the job
 // gives it, so that AddressSanitizer / UBSan (`make wiresan`) see any read or write past a
 // bound. CPU only; no device code runs.
@@ -17,7 +17,7 @@
 #include <string>
 #include <vector>
 
-#include "../narwhal_amd/csrc/nw_wiredec.hpp"
+#include "wire_single.hpp"
 
 using namespace nw::wd;
 typedef std::string bytes;
@@ -142,46 +142,33 @@ static void run(const bytes& f, uint32_t mis, uint32_t lanes, uint32_t group, co
     if (r.kind != 1) return;
     uint32_t ids[8], org[8], aut[8], sg[16];
     uint64_t round;
-    out_t o{};
-    o.v_ids = ids; o.v_rounds = &round; o.v_origins = org; o.v_authors = aut; o.v_sigs = sg;
-    o.nvmsg = 1;
-    for (uint32_t l = 0; l < group; ++l) emit_lane(w.data(), mis, len, r, dst_t{0, 0, 0}, o, l, group);
+    wire_single_t s(1, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, ids, &round, org, aut,
+                    sg);
+    s.emit<false>(w.data(), mis, len, r, nullptr, nullptr, 0, group);
     return;
   }
-  std::vector<uint32_t> order(canon_list_words(mis + len));
-  canon_t c{0, 0, kCanonNone, 0};
-  canon_job_t jb;
-  c.state = canon_begin(w.data(), mis, len, r, order.size(), &jb);
+  const wire_canon_t cr(w.data(), mis, len, r, lanes);
+  const canon_t& c = cr.c;
   if (c.state == kCanonOver) ++g_over;
   if (c.state == kCanonDone) {
     ++g_canon;
-    std::vector<uint32_t> keys(8 * (size_t)(r.np + r.nq)), kept(r.np + r.nq);
-    for (uint32_t l = 0; l < lanes; ++l) canon_stage(l, lanes, jb, keys.data());
-    for (uint32_t l = 0; l < lanes; ++l) canon_mark(l, lanes, jb, keys.data(), kept.data());
-    for (uint32_t l = 0; l < lanes; ++l) canon_rank(l, lanes, jb, keys.data(), kept.data(), order.data(), &c);
     if (expect && (c.np_u != expect->np_u || c.nq_u != expect->nq_u)) abort();
   } else if (!r.canonical && c.state != kCanonOver) {
     abort();   // a record of this very frame always passes canon_begin's bounds
   }
   if (!r.canonical && c.state != kCanonDone) return;
-  const uint64_t hl = r.canonical ? header_len(r) : header_len(c);
-  const int k = r.kind == 2;
+  const uint64_t hl = r.canonical ? header_len(r.np, r.nq) : header_len(c.np_u, c.nq_u);
   std::vector<uint8_t> hb(hl);
   std::vector<uint32_t> id(8), sig(16), vpk(8 * (size_t)r.nv), vsig(16 * (size_t)r.nv);
-  uint64_t ho[2], vo[2];
-  uint32_t pc;
-  out_t o{};
-  o.hb[k] = hb.data(); o.hb_len[k] = hl; o.ho[k] = ho; o.pc[k] = &pc;
-  o.ids[k] = id.data(); o.sigs[k] = sig.data(); o.nitems[k] = 1;
-  o.vo = vo; o.vpk = vpk.data(); o.vsig = vsig.data(); o.nvotes = r.nv;
-  for (uint32_t l = 0; l < group; ++l) {
-    if (r.canonical) emit_lane(w.data(), mis, len, r, dst_t{0, 0, 0}, o, l, group);
-    else emit_lane_canon(w.data(), mis, len, r, c, order.data(), order.size(), dst_t{0, 0, 0}, o, l, group);
-  }
+  wire_single_t s(r.kind, hb.data(), hl, id.data(), sig.data(), vpk.data(), vsig.data(), r.nv,
+                  nullptr, nullptr, nullptr, nullptr, nullptr);
+  // a canonical frame: first the plain instance, which gets no canon_t and no order list
+  if (r.canonical) s.emit<false>(w.data(), mis, len, r, nullptr, nullptr, 0, group);
+  s.emit<true>(w.data(), mis, len, r, &c, cr.order.data(), cr.order.size(), group);
   if (expect) {
     // (the author's 32 bytes are the key's first 32; gen() encodes exactly 32)
     if (hl != expect->hb.size() || memcmp(hb.data(), expect->hb.data(), hl) != 0) abort();
-    if (pc != expect->np_u) abort();
+    if (s.pc != expect->np_u) abort();
   }
 }
 

@@ -4,23 +4,44 @@
 // nw_wire.hip run against the Python restatement of the wire format, without a GPU. The
 // emit is cooperative: every lane index of the group runs in a loop. wc_canon / wc_emit_canon
 // (tests/test_wire_canon_cpu.py) do the same for the canonicalisation of non-canonical
-// frames: each phase for every lane index, one phase after the other.
-#include <stdlib.h>
+// frames: each phase for every lane index, one phase after the other. wc_place / wc_emit_rec
+// (tests/test_wire_place_cpu.py): the host's placement (nw_wireplace.hpp) and the emit over
+// the caller's records, forged ones included.
 #include <string.h>
 
+#include <algorithm>
 #include <vector>
 
-#include "../narwhal_amd/csrc/nw_wiredec.hpp"
+#include "../narwhal_amd/csrc/nw_wireplace.hpp"
+#include "wire_single.hpp"
 
 using namespace nw::wd;
 
 // The frame at byte offset `misalign` (0..3) of a word buffer, as the kernels see a frame
 // that starts anywhere in the call's byte stream. The bytes around it are 0xA5: nothing
 // outside the frame may reach a result.
-static std::vector<uint32_t> place(const uint8_t* frame, uint64_t len, uint32_t misalign) {
+static std::vector<uint32_t> in_words(const uint8_t* frame, uint64_t len, uint32_t misalign) {
   std::vector<uint32_t> w((misalign + len + 3) / 4 + 1, 0xa5a5a5a5u);
   if (len) memcpy(reinterpret_cast<uint8_t*>(w.data()) + misalign, frame, len);
   return w;
+}
+
+// Emits the placed frame with record r (c: its canonicalisation, or null for the plain
+// instance) over the buffers of wc_emit, and returns what wc_emit returns.
+static long emit_one(const uint32_t* w, uint32_t misalign, uint64_t len, uint32_t group,
+                     const rec_t& r, const wire_canon_t* c, uint8_t* hb, uint64_t hb_cap,
+                     uint8_t* id32, uint8_t* sig64, uint8_t* vpk, uint8_t* vsig, uint32_t vcap,
+                     uint32_t* pc_out, uint64_t* off3_out, uint8_t* vote168) {
+  wire_single_t s(r.kind, hb, hb_cap, id32, sig64, vpk, vsig, vcap, vote168, vote168 + 32,
+                  vote168 + 40, vote168 + 72, vote168 + 104);
+  if (c) s.emit<true>(w, misalign, len, r, &c->c, c->order.data(), c->order.size(), group);
+  else s.emit<false>(w, misalign, len, r, nullptr, nullptr, 0, group);
+  if (r.kind == 1) return 0;
+  *pc_out = s.pc;
+  off3_out[0] = s.ho[0];
+  off3_out[1] = s.ho[1];
+  off3_out[2] = r.kind == 2 ? s.vo[1] : 0;
+  return (long)(c ? header_len(c->c.np_u, c->c.nq_u) : header_len(r.np, r.nq));
 }
 
 extern "C" {
@@ -28,10 +49,28 @@ extern "C" {
 // rec8: kind, canonical, np, nq, nv, alen, vlen, 0 (wd::rec_t). Returns the kind.
 int wc_scan(const uint8_t* frame, uint64_t len, uint32_t misalign, uint32_t* rec8) {
   misalign &= 3;
-  const std::vector<uint32_t> w = place(frame, len, misalign);
+  const std::vector<uint32_t> w = in_words(frame, len, misalign);
   const rec_t r = scan(w.data(), misalign, len);
   memcpy(rec8, &r, sizeof r);
   return r.kind;
+}
+
+// wc_emit with the caller's record r (as wc_scan writes it, or forged: a record that does
+// not fit the frame must write nothing) in place of the scan and of the buffer size checks.
+// can != null: the instance that serves canonicalised frames, with the caller's canon_t and
+// the frame's own order list. What is not written keeps the caller's bytes.
+long wc_emit_rec(const uint8_t* frame, uint64_t len, uint32_t misalign, uint32_t group,
+                 const rec_t* r, const canon_t* can, uint8_t* hb, uint64_t hb_cap, uint8_t* id32,
+                 uint8_t* sig64, uint8_t* vpk, uint8_t* vsig, uint32_t vcap, uint32_t* pc_out,
+                 uint64_t* off3_out, uint8_t* vote168) {
+  misalign &= 3;
+  if (group == 0 || (r->kind != 0 && r->kind != 1 && r->kind != 2)) return -1;
+  const std::vector<uint32_t> w = in_words(frame, len, misalign);
+  const rec_t none{-1, 0, 0, 0, 0, 0, 0, 0};   // (can = null: nothing to canonicalise)
+  wire_canon_t c(w.data(), misalign, len, can ? scan(w.data(), misalign, len) : none, 64);
+  if (can) c.c = *can;
+  return emit_one(w.data(), misalign, len, group, *r, can ? &c : nullptr, hb, hb_cap, id32, sig64,
+                  vpk, vsig, vcap, pc_out, off3_out, vote168);
 }
 
 // Scans and emits one frame with a group of `group` lanes. Header / Certificate: hb (hb_cap
@@ -42,77 +81,12 @@ long wc_emit(const uint8_t* frame, uint64_t len, uint32_t misalign, uint32_t gro
              uint64_t hb_cap, uint8_t* id32, uint8_t* sig64, uint8_t* vpk, uint8_t* vsig,
              uint32_t vcap, uint32_t* pc_out, uint64_t* off3_out, uint8_t* vote168) {
   misalign &= 3;
-  if (group == 0) return -1;
-  const std::vector<uint32_t> w = place(frame, len, misalign);
+  const std::vector<uint32_t> w = in_words(frame, len, misalign);
   const rec_t r = scan(w.data(), misalign, len);
-  if (r.kind != 0 && r.kind != 1 && r.kind != 2) return -1;
-  if (r.kind != 1 && !r.canonical) return -1;
-  const dst_t d{0, 0, 0};
-  uint64_t ho[2] = {~0ull, ~0ull}, vo[2] = {~0ull, ~0ull}, round = 0;
-  uint32_t pc = ~0u;
-  out_t o{};
-  const int k = r.kind == 2 ? 1 : 0;
-  if (r.kind == 1) {
-    o.v_ids = reinterpret_cast<uint32_t*>(vote168);
-    o.v_rounds = &round;
-    o.v_origins = reinterpret_cast<uint32_t*>(vote168 + 40);
-    o.v_authors = reinterpret_cast<uint32_t*>(vote168 + 72);
-    o.v_sigs = reinterpret_cast<uint32_t*>(vote168 + 104);
-    o.nvmsg = 1;
-  } else {
-    if (header_len(r) > hb_cap || r.nv > vcap) return -1;
-    o.hb[k] = hb;
-    o.hb_len[k] = hb_cap;
-    o.ho[k] = ho;
-    o.pc[k] = &pc;
-    o.ids[k] = reinterpret_cast<uint32_t*>(id32);
-    o.sigs[k] = reinterpret_cast<uint32_t*>(sig64);
-    o.nitems[k] = 1;
-    o.vo = vo;
-    o.vpk = reinterpret_cast<uint32_t*>(vpk);
-    o.vsig = reinterpret_cast<uint32_t*>(vsig);
-    o.nvotes = vcap;
-  }
-  for (uint32_t lane = 0; lane < group; ++lane)
-    emit_lane(w.data(), misalign, len, r, d, o, lane, group);
-  if (r.kind == 1) {
-    memcpy(vote168 + 32, &round, 8);
-    return 0;
-  }
-  *pc_out = pc;
-  off3_out[0] = ho[0];
-  off3_out[1] = ho[1];
-  off3_out[2] = k ? vo[1] : 0;
-  return (long)header_len(r);
+  if (r.kind != 1 && (!r.canonical || header_len(r.np, r.nq) > hb_cap || r.nv > vcap)) return -1;
+  return wc_emit_rec(frame, len, misalign, group, &r, nullptr, hb, hb_cap, id32, sig64, vpk, vsig, vcap,
+                     pc_out, off3_out, vote168);
 }
-
-}  // extern "C"
-
-// The canonicalisation of one placed frame as k_wire_canon runs it: every phase for every
-// lane index, one phase after the other (the loop boundary is the kernel's barrier). The
-// scratch is sized as the job sizes it, for a byte stream that ends with this frame.
-struct canon_run_t {
-  canon_t c{0, 0, kCanonNone, 0};
-  std::vector<uint32_t> order;
-  uint64_t list = 0;
-};
-static canon_run_t run_canon(const uint32_t* w, uint32_t misalign, uint64_t len, const rec_t& r,
-                             uint32_t lanes) {
-  canon_run_t out;
-  out.order.assign(canon_list_words(misalign + len), 0xdeadbeefu);
-  canon_job_t jb;
-  out.c.state = canon_begin(w, misalign, len, r, out.order.size(), &jb);
-  if (out.c.state != kCanonDone) return out;
-  out.list = jb.list;
-  std::vector<uint32_t> keys(8 * kCanonMax, 0xa5a5a5a5u), kept(kCanonMax, 0xa5a5a5a5u);
-  for (uint32_t l = 0; l < lanes; ++l) canon_stage(l, lanes, jb, keys.data());
-  for (uint32_t l = 0; l < lanes; ++l) canon_mark(l, lanes, jb, keys.data(), kept.data());
-  for (uint32_t l = 0; l < lanes; ++l)
-    canon_rank(l, lanes, jb, keys.data(), kept.data(), out.order.data(), &out.c);
-  return out;
-}
-
-extern "C" {
 
 // Scans one frame and canonicalises it with `lanes` lanes. Returns the state (kCanon*: 0 not
 // applicable, 1 canonicalised, 2 over the bound) or -1 if order_cap is too small. For state
@@ -123,9 +97,9 @@ int wc_canon(const uint8_t* frame, uint64_t len, uint32_t misalign, uint32_t lan
              uint32_t* nq_u, uint32_t* order, uint32_t order_cap, uint32_t* touched) {
   misalign &= 3;
   if (lanes == 0) return -1;
-  const std::vector<uint32_t> w = place(frame, len, misalign);
+  const std::vector<uint32_t> w = in_words(frame, len, misalign);
   const rec_t r = scan(w.data(), misalign, len);
-  const canon_run_t c = run_canon(w.data(), misalign, len, r, lanes);
+  const wire_canon_t c(w.data(), misalign, len, r, lanes);
   uint32_t t = 0;
   for (uint32_t x : c.order) t += x != 0xdeadbeefu;
   *touched = t;
@@ -148,35 +122,31 @@ long wc_emit_canon(const uint8_t* frame, uint64_t len, uint32_t misalign, uint32
                    uint64_t* off3_out) {
   misalign &= 3;
   if (group == 0 || lanes == 0) return -1;
-  const std::vector<uint32_t> w = place(frame, len, misalign);
+  const std::vector<uint32_t> w = in_words(frame, len, misalign);
   const rec_t r = scan(w.data(), misalign, len);
-  const canon_run_t c = run_canon(w.data(), misalign, len, r, lanes);
+  const wire_canon_t c(w.data(), misalign, len, r, lanes);
   if (c.c.state != kCanonDone) return -1;
-  if (header_len(c.c) > hb_cap || r.nv > vcap) return -1;
-  const dst_t d{0, 0, 0};
-  uint64_t ho[2] = {~0ull, ~0ull}, vo[2] = {~0ull, ~0ull};
-  uint32_t pc = ~0u;
-  out_t o{};
-  const int k = r.kind == 2 ? 1 : 0;
-  o.hb[k] = hb;
-  o.hb_len[k] = hb_cap;
-  o.ho[k] = ho;
-  o.pc[k] = &pc;
-  o.ids[k] = reinterpret_cast<uint32_t*>(id32);
-  o.sigs[k] = reinterpret_cast<uint32_t*>(sig64);
-  o.nitems[k] = 1;
-  o.vo = vo;
-  o.vpk = reinterpret_cast<uint32_t*>(vpk);
-  o.vsig = reinterpret_cast<uint32_t*>(vsig);
-  o.nvotes = vcap;
-  for (uint32_t lane = 0; lane < group; ++lane)
-    emit_lane_canon(w.data(), misalign, len, r, c.c, c.order.data(), c.order.size(), d, o, lane,
-                    group);
-  *pc_out = pc;
-  off3_out[0] = ho[0];
-  off3_out[1] = ho[1];
-  off3_out[2] = k ? vo[1] : 0;
-  return (long)header_len(c.c);
+  if (header_len(c.c.np_u, c.c.nq_u) > hb_cap || r.nv > vcap) return -1;
+  uint8_t no_vote[168];   // (a Header / Certificate: not written)
+  return emit_one(w.data(), misalign, len, group, r, &c, hb, hb_cap, id32, sig64, vpk, vsig, vcap,
+                  pc_out, off3_out, no_vote);
+}
+
+// The host's placement (nw_wireplace.hpp) of n frames (fo: their n + 1 offsets) by the
+// caller's records (cans: null = canonicalisation off). cvo (n + 1) / host (n): the vote
+// offsets and the host-frame list, their lengths in counts2. Returns the error string, or null.
+const char* wc_place(const rec_t* recs, const canon_t* cans, const uint64_t* fo, uint64_t n,
+                     uint64_t total, uint64_t vbound, dst_t* dst, place_t* totals, uint64_t* cvo,
+                     uint64_t* host, uint64_t* counts2, int32_t* kind, int32_t* status,
+                     uint64_t* index) {
+  std::vector<uint64_t> cv, hf;
+  const char* bad =
+      place(recs, cans, fo, n, total, vbound, dst, totals, &cv, &hf, kind, status, index);
+  std::copy(cv.begin(), cv.end(), cvo);
+  std::copy(hf.begin(), hf.end(), host);
+  counts2[0] = cv.size();
+  counts2[1] = hf.size();
+  return bad;
 }
 
 }  // extern "C"
