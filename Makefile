@@ -1,6 +1,6 @@
 # Builds the MI355X engine (narwhal_amd/libnarwhal_amd.so, gfx950 only), the CPU oracle
-# (test infrastructure) and the host check libraries of the kernels' arithmetic and of the wire
-# decoder (test infrastructure).
+# (test infrastructure) and the host check libraries of the kernels' arithmetic, of the wire
+# decoder and of the message jobs' staging layout (test infrastructure).
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Iinclude -Inarwhal_amd/csrc -Wall -Wno-unused-function
@@ -9,7 +9,7 @@ HDRS := $(wildcard $(CSRC)/*.hpp) $(CSRC)/nw_kernels.h $(CSRC)/nw_runtime.h $(CS
 LIB := narwhal_amd/libnarwhal_amd.so
 BUILD := build
 
-all: $(LIB) oracle hostcheck wirecheck loadgen
+all: $(LIB) oracle hostcheck wirecheck stagecheck loadgen
 
 $(BUILD)/nw_kernels.o: $(CSRC)/nw_kernels.hip $(HDRS)
 	@mkdir -p $(BUILD)
@@ -73,6 +73,17 @@ wiresan: tools/wire_canon_san
 tools/wire_canon_san: tools/wire_canon_san.cpp tools/wire_single.hpp $(CSRC)/nw_wiredec.hpp
 	g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all $< -o $@
 
+# the message jobs' staging layout (nw_stage.hpp) over malloc'ed buffers (tests/test_stage_cpu.py)
+stagecheck: tools/libnw_stagecheck.so
+tools/libnw_stagecheck.so: tools/stagecheck.hip $(CSRC)/nw_stage.hpp include/narwhal_amd.h
+	$(HIPCC) --cuda-host-only -O2 -std=c++17 -fPIC -shared -Iinclude $< -o $@
+
+# the same file with its main under AddressSanitizer / UBSan, as a stand-alone CPU program (not
+# part of `all`): make stagesan && tools/stage_san
+stagesan: tools/stage_san
+tools/stage_san: tools/stagecheck.hip $(CSRC)/nw_stage.hpp include/narwhal_amd.h
+	g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -DSTAGECHECK_MAIN -Iinclude -x c++ $< -o $@
+
 loadgen: tools/libnw_loadgen.so
 tools/libnw_loadgen.so: tools/nw_loadgen.cpp include/narwhal_amd.h $(LIB)
 	g++ -O2 -std=c++17 -fPIC -shared -Iinclude $< -o $@ -Lnarwhal_amd -lnarwhal_amd -Wl,-rpath,'$$ORIGIN/../narwhal_amd' -pthread
@@ -91,7 +102,7 @@ tools/ubench_valu: tools/ubench_valu.hip
 	$(HIPCC) --offload-arch=$(ARCH) -O3 $< -o $@
 
 clean:
-	rm -rf $(BUILD) $(LIB) tools/libnw_hostcheck.so tools/libnw_wirecheck.so tools/libnw_loadgen.so tools/service_stress tools/service_stress_tsan tools/wire_canon_san
+	rm -rf $(BUILD) $(LIB) tools/libnw_hostcheck.so tools/libnw_wirecheck.so tools/libnw_stagecheck.so tools/libnw_loadgen.so tools/service_stress tools/service_stress_tsan tools/wire_canon_san tools/stage_san
 	$(MAKE) -s -C oracle clean
 
-.PHONY: all oracle hostcheck wirecheck wiresan loadgen stress ubench clean
+.PHONY: all oracle hostcheck wirecheck stagecheck wiresan stagesan loadgen stress ubench clean

@@ -38,6 +38,7 @@
 #include "narwhal_amd.h"
 #include "nw_kernels.h"
 #include "nw_runtime.h"
+#include "nw_stage.hpp"
 #include "nw_wireplace.hpp"
 
 struct nw_job {
@@ -80,6 +81,7 @@ struct nw_job {
 namespace {
 
 using nw::rt::set_err;
+using nw::stage::a256;
 
 constexpr int kMaxDev = 64;
 
@@ -93,13 +95,24 @@ struct DevPool {
 };
 DevPool g_pool[kMaxDev];
 
-inline size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 #define JOB_HIP(call, what)                                      \
   do {                                                           \
     hipError_t e_ = (call);                                      \
     if (e_ != hipSuccess) return set_err(NW_E_DEVICE, what, e_); \
   } while (0)
+
+// Environment knobs. A flag that is off by default is switched on by NAME=1, one that is on
+// by default is switched off by NAME=0; every other value leaves the default. An integer knob
+// is read as a decimal number (unset or empty: def); its bounds are the reader's. The knobs
+// read once per process keep their value in a function-local static.
+bool env_flag(const char* name, bool def) {
+  const char* e = getenv(name);
+  return def ? !(e && *e == '0') : (e && *e == '1');
+}
+long long env_int(const char* name, long long def) {
+  const char* e = getenv(name);
+  return e && *e ? atoll(e) : def;
+}
 
 int job_acquire(int dev, nw_job** out) {
   int rc = nw::rt::use_device(dev);
@@ -242,24 +255,17 @@ int job_reserve(nw_job* j, size_t hbytes, size_t dbytes) {
 // Outputs stay in the pinned buffer. Falls back to the pinned inputs when the device memory
 // has no host mapping.
 bool small_vram() {
-  static const bool on = [] {
-    const char* e = getenv("NW_SMALL_VRAM");
-    return e && *e == '1';
-  }();
+  static const bool on = env_flag("NW_SMALL_VRAM", false);
   return on;
 }
 bool test_fuse_abort() {
-  static std::atomic<long> left{[] {
-    const char* e = getenv("NW_TEST_FUSE_ABORT");
-    return e && *e ? atol(e) : 0L;
-  }()};
+  static std::atomic<long> left{(long)env_int("NW_TEST_FUSE_ABORT", 0)};
   if (left.load(std::memory_order_relaxed) <= 0) return false;
   return left.fetch_sub(1, std::memory_order_relaxed) > 0;
 }
 bool test_stale_flags() {
   static const bool on = [] {
-    const char* e = getenv("NW_TEST_STALE_FLAGS");
-    const bool v = e && *e == '1';
+    const bool v = env_flag("NW_TEST_STALE_FLAGS", false);
     if (v) fprintf(stderr, "[narwhal_amd] NW_TEST_STALE_FLAGS: small-job flag words poisoned\n");
     return v;
   }();
@@ -274,10 +280,7 @@ uint32_t next_done_seq() {
   return v;
 }
 bool small_done() {   // on unless NW_SMALL_DONE=0
-  static const bool on = [] {
-    const char* e = getenv("NW_SMALL_DONE");
-    return !(e && *e == '0');
-  }();
+  static const bool on = env_flag("NW_SMALL_DONE", true);
   return on;
 }
 // Outputs delivered from a job whose kernels have written them (done word / flags) while the
@@ -298,37 +301,24 @@ bool small_flags_done(const nw_job* j) {
   return true;
 }
 bool batch_spin() {   // on unless NW_BATCH_SPIN=0 (profiles/r06n: wait 258 vs 264 us)
-  static const bool on = [] {
-    const char* e = getenv("NW_BATCH_SPIN");
-    return !(e && *e == '0');
-  }();
+  static const bool on = env_flag("NW_BATCH_SPIN", true);
   return on;
 }
 bool batch_stamps() {
-  static const bool on = [] {
-    const char* e = getenv("NW_BATCH_STAMPS");
-    return e && *e == '1';
-  }();
+  static const bool on = env_flag("NW_BATCH_STAMPS", false);
   return on;
 }
 // votes per input-gate flag, a multiple of 64 (NW_GATE_CHUNK=k, A/B hook, rounded up to 64)
 const uint64_t kGateChunk = [] {
-  const char* e = getenv("NW_GATE_CHUNK");
-  const long v = e && *e ? atol(e) : 1024L;
+  const long long v = env_int("NW_GATE_CHUNK", 1024);
   return (uint64_t)(v < 64 ? 64 : (v + 63) / 64 * 64);
 }();
 bool batch_gate() {
-  static const bool on = [] {
-    const char* e = getenv("NW_BATCH_GATE");
-    return e && *e == '1';
-  }();
+  static const bool on = env_flag("NW_BATCH_GATE", false);
   return on;
 }
 bool batch_vram() {   // on unless NW_BATCH_VRAM=0 (profiles/r06d: config 1 0.303 vs 0.321 ms)
-  static const bool on = [] {
-    const char* e = getenv("NW_BATCH_VRAM");
-    return !(e && *e == '0');
-  }();
+  static const bool on = env_flag("NW_BATCH_VRAM", true);
   return on;
 }
 bool mapped_rw(const void* p, size_t bytes) {
@@ -719,68 +709,70 @@ int submit_sha(int dev, const uint8_t* data, const uint64_t* offsets, const uint
 }
 
 // ---- primary messages ------------------------------------------------------------------
-// 256-byte aligned sections of a job's staging buffers (pinned and device share one layout).
-struct Packer {
-  size_t off = 0;
-  size_t add(size_t bytes) {
-    const size_t o = off;
-    off += a256(bytes ? bytes : 1);
-    return o;
+// The sections of a job's staging buffers (pinned and device share one layout): nw_stage.hpp
+// states the committee's, the header stream's, the certificate votes' and the Vote messages';
+// what follows them (slots, statuses, indices, flags, workspace) is each job's own.
+namespace stg = nw::stage;
+using stg::Packer;
+
+// The staged arrays as the kernels' structs take them (words where the public structs say
+// bytes; the emit writes through its pointers, into a device region that is the job's own).
+const uint32_t* w32(const void* p) { return static_cast<const uint32_t*>(p); }
+uint32_t* w32_out(const void* p) { return const_cast<uint32_t*>(w32(p)); }
+void small_inputs(nw::small_job_t& J, const nw_committee& c, const nw_certificates& d,
+                  const uint8_t* z16, const stg::VoteMsgs& v) {
+  J.com = nw::cert_committee_t{c.nauth, w32(c.pks), c.stakes, c.worker_offsets, c.worker_ids};
+  J.hb = d.header_bytes;
+  J.ho = d.header_offsets;
+  J.pc = d.payload_counts;
+  J.ids = w32(v.ids ? v.ids : d.ids);   // the Vote messages' header ids, or the headers'
+  J.hsig = w32(d.header_sigs);
+  J.vpk = w32(d.vote_pks);
+  J.vsig = w32(d.vote_sigs);
+  J.z16 = w32(z16);
+  J.rounds = v.rounds;
+  J.origins = w32(v.origins);
+  J.authors = w32(v.authors);
+  J.sigs = w32(v.sigs);
+}
+nw::wd::out_t wire_out(const nw_certificates (&d)[2], const stg::VoteMsgs& v) {
+  nw::wd::out_t out{};
+  for (int k = 0; k < 2; ++k) {
+    out.hb[k] = const_cast<uint8_t*>(d[k].header_bytes);
+    out.hb_len[k] = d[k].header_bytes_len;
+    out.ho[k] = const_cast<uint64_t*>(d[k].header_offsets);
+    out.pc[k] = const_cast<uint32_t*>(d[k].payload_counts);
+    out.ids[k] = w32_out(d[k].ids);
+    out.sigs[k] = w32_out(d[k].header_sigs);
+    out.nitems[k] = (uint32_t)d[k].n;
   }
-};
-
-void put(nw_job* j, size_t off, const void* src, size_t bytes) {
-  if (bytes) memcpy(j->hbuf + off, src, bytes);
-}
-
-// The committee's arrays in the staging buffer; returns its device view.
-struct CommitteeOffs {
-  size_t pks, stakes, wo, wi;
-};
-CommitteeOffs plan_committee(Packer& P, const nw_committee* com) {
-  const size_t na = com->nauth, nwk = na ? com->worker_offsets[na] : 0;
-  CommitteeOffs o;
-  o.pks = P.add(32 * na);
-  o.stakes = P.add(4 * na);
-  o.wo = P.add(8 * (na + 1));
-  o.wi = P.add(4 * nwk);
-  return o;
-}
-nw_committee stage_committee(nw_job* j, const CommitteeOffs& o, const nw_committee* com) {
-  const size_t na = com->nauth, nwk = na ? com->worker_offsets[na] : 0;
-  put(j, o.pks, com->pks, 32 * na);
-  put(j, o.stakes, com->stakes, 4 * na);
-  put(j, o.wo, com->worker_offsets, 8 * (na + 1));
-  put(j, o.wi, com->worker_ids, 4 * nwk);
-  nw_committee d;
-  d.nauth = na;
-  d.pks = reinterpret_cast<const uint8_t*>(j->dbuf + o.pks);
-  d.stakes = reinterpret_cast<const uint32_t*>(j->dbuf + o.stakes);
-  d.worker_offsets = reinterpret_cast<const uint64_t*>(j->dbuf + o.wo);
-  d.worker_ids = reinterpret_cast<const uint32_t*>(j->dbuf + o.wi);
-  return d;
+  out.vo = const_cast<uint64_t*>(d[1].vote_offsets);
+  out.vpk = w32_out(d[1].vote_pks);
+  out.vsig = w32_out(d[1].vote_sigs);
+  out.nvotes = (uint32_t)d[1].nvotes;
+  out.v_ids = w32_out(v.ids);
+  out.v_rounds = const_cast<uint64_t*>(v.rounds);
+  out.v_origins = w32_out(v.origins);
+  out.v_authors = w32_out(v.authors);
+  out.v_sigs = w32_out(v.sigs);
+  out.nvmsg = (uint32_t)v.n;
+  return out;
 }
 
 // ---- small jobs: one launch (nw_small.hip) ----------------------------------------------
 // NW_SMALL=0 turns the small-job path off, NW_SMALL=1 takes it whenever it applies whatever
 // the size (test hook); NW_SMALL_MAX_SLOTS = the largest job (signatures) it takes by default.
-int small_mode() {
-  const char* e = getenv("NW_SMALL");
-  return e && *e ? atoi(e) : -1;
-}
+// (These and NW_SMALL_S are read on every call: tests and tools change them within a process.)
+int small_mode() { return (int)env_int("NW_SMALL", -1); }
 uint64_t small_max_slots() {
-  const char* e = getenv("NW_SMALL_MAX_SLOTS");
-  const long long v = e && *e ? atoll(e) : 0;
+  const long long v = env_int("NW_SMALL_MAX_SLOTS", 0);
   return v > 0 ? (uint64_t)v : 65536;
 }
 // Slots per workgroup: the fewest (shortest comb chains) that keep the grid within ~2
 // workgroups per CU.
 uint32_t small_slots_per_wg(uint64_t nslots) {
-  const char* e = getenv("NW_SMALL_S");   // test hook: a fixed S (4, 8, 16, 32 or 64)
-  if (e && *e) {
-    const int s = atoi(e);
-    if (s == 4 || s == 8 || s == 16 || s == 32 || s == 64) return (uint32_t)s;
-  }
+  const int s = (int)env_int("NW_SMALL_S", 0);   // test hook: a fixed S (4, 8, 16, 32 or 64)
+  if (s == 4 || s == 8 || s == 16 || s == 32 || s == 64) return (uint32_t)s;
   uint32_t S = 4;
   while (S < 64 && (nslots + S - 1) / S > 512) S *= 2;
   return S;
@@ -809,13 +801,8 @@ int job_counters(nw_job* j, size_t n) {
 // when it took the job, 1 when the job does not qualify (size, committee, key tables not
 // built for this committee yet: the caller runs the ordinary pipeline, which builds them),
 // or a negative NW_E_*. cs: certificates / headers; for votes the vote arrays.
-struct VoteArrays {
-  const uint8_t *ids, *origins, *authors, *sigs;
-  const uint64_t* rounds;
-  size_t n;
-};
 int submit_small(int dev, uint32_t kind, const nw_committee* com, const nw_certificates* cs,
-                 const VoteArrays* va, const uint8_t* z16, int32_t* status_out,
+                 const stg::VoteMsgs* va, const uint8_t* z16, int32_t* status_out,
                  uint64_t* index_out, nw_job** job) {
   const int mode = small_mode();
   if (mode == 0) return 1;
@@ -842,25 +829,20 @@ int submit_small(int dev, uint32_t kind, const nw_committee* com, const nw_certi
   nw_job* j;
   int rc = job_acquire(dev, &j);
   if (rc) return rc;
+  // the kind's groups are planned; the others stay unstaged (null in the kernel's view)
   Packer P;
-  const size_t nwk = com->worker_offsets[na];
-  const size_t o_pk = P.add(32 * na), o_stk = P.add(4 * na), o_wo = P.add(8 * (na + 1)),
-               o_wi = P.add(4 * nwk);
-  size_t o_hb = 0, o_ho = 0, o_pc = 0, o_id = 0, o_hs = 0, o_vp = 0, o_vs = 0, o_z = 0;
-  size_t o_rd = 0, o_or = 0, o_au = 0, o_sg = 0;
-  uint64_t hb0 = 0, hlen = 0;
+  const stg::CommitteeOffs oc = stg::plan_committee(P, com);
+  stg::HeaderOffs oh;
+  stg::CertVoteOffs ov;
+  stg::VoteMsgOffs om;
+  uint64_t hlen = 0;
   if (kind == nw::kSmallVotes) {
-    o_id = P.add(32 * n); o_rd = P.add(8 * n); o_or = P.add(32 * n); o_au = P.add(32 * n);
-    o_sg = P.add(64 * n);
+    om = stg::plan_vote_msgs(P, n);
   } else {
-    hb0 = cs->header_offsets[0];
-    hlen = cs->header_offsets[n] - hb0;
-    o_hb = P.add(hlen); o_ho = P.add(8 * (n + 1)); o_pc = P.add(4 * n); o_id = P.add(32 * n);
-    o_hs = P.add(64 * n);
-    if (kind == nw::kSmallCerts) {
-      o_vp = P.add(32 * nv); o_vs = P.add(64 * nv);
-      if (z16) o_z = P.add(16 * nv);
-    }
+    hlen = cs->header_offsets[n] - cs->header_offsets[0];
+    oh = stg::plan_headers(P, n, hlen);
+    // (no vote offsets: the slots carry each vote's certificate and position)
+    if (kind == nw::kSmallCerts) ov = stg::plan_cert_votes(P, n, nv, false, z16 != nullptr);
   }
   const size_t o_sl = P.add(sizeof(nw::small_slot_t) * nslots);
   const size_t o_st = P.add(4 * n), o_ix = P.add(8 * n);
@@ -873,29 +855,15 @@ int submit_small(int dev, uint32_t kind, const nw_committee* com, const nw_certi
   if (!rc) rc = job_counters(j, n);
   if (rc) return job_abort(j, rc);
   char* H = j->hbuf;
-  put(j, o_pk, com->pks, 32 * na);
-  put(j, o_stk, com->stakes, 4 * na);
-  put(j, o_wo, com->worker_offsets, 8 * (na + 1));
-  put(j, o_wi, com->worker_ids, 4 * nwk);
+  stg::fill_committee(H, oc, com);
   nw::small_slot_t* sl = reinterpret_cast<nw::small_slot_t*>(H + o_sl);
   if (kind == nw::kSmallVotes) {
-    put(j, o_id, va->ids, 32 * n);
-    put(j, o_rd, va->rounds, 8 * n);
-    put(j, o_or, va->origins, 32 * n);
-    put(j, o_au, va->authors, 32 * n);
-    put(j, o_sg, va->sigs, 64 * n);
+    stg::fill_vote_msgs(H, om, *va);
     for (size_t i = 0; i < n; ++i) sl[i] = {(uint32_t)i, 0u, 0u, 1u};
   } else {
-    put(j, o_hb, cs->header_bytes + hb0, hlen);
-    uint64_t* ho = reinterpret_cast<uint64_t*>(H + o_ho);
-    for (size_t i = 0; i <= n; ++i) ho[i] = cs->header_offsets[i] - hb0;
-    put(j, o_pc, cs->payload_counts, 4 * n);
-    put(j, o_id, cs->ids, 32 * n);
-    put(j, o_hs, cs->header_sigs, 64 * n);
+    stg::fill_headers(H, oh, cs);
     if (kind == nw::kSmallCerts) {
-      put(j, o_vp, cs->vote_pks, 32 * nv);
-      put(j, o_vs, cs->vote_sigs, 64 * nv);
-      if (z16) put(j, o_z, z16, 16 * nv);
+      stg::fill_cert_votes(H, ov, cs, z16);
       size_t s = 0;
       for (size_t i = 0; i < n; ++i) {
         const uint32_t v0 = (uint32_t)cs->vote_offsets[i];
@@ -922,28 +890,9 @@ int submit_small(int dev, uint32_t kind, const nw_committee* com, const nw_certi
   J.slots_per_wg = small_slots_per_wg(nslots);
   J.nmsg = n;
   J.nslots = nslots;
-  J.com = nw::cert_committee_t{na, reinterpret_cast<const uint32_t*>(X + o_pk),
-                               reinterpret_cast<const uint32_t*>(X + o_stk),
-                               reinterpret_cast<const uint64_t*>(X + o_wo),
-                               reinterpret_cast<const uint32_t*>(X + o_wi)};
-  if (kind == nw::kSmallVotes) {
-    J.ids = reinterpret_cast<const uint32_t*>(X + o_id);
-    J.rounds = reinterpret_cast<const uint64_t*>(X + o_rd);
-    J.origins = reinterpret_cast<const uint32_t*>(X + o_or);
-    J.authors = reinterpret_cast<const uint32_t*>(X + o_au);
-    J.sigs = reinterpret_cast<const uint32_t*>(X + o_sg);
-  } else {
-    J.hb = reinterpret_cast<const uint8_t*>(X + o_hb);
-    J.ho = reinterpret_cast<const uint64_t*>(X + o_ho);
-    J.pc = reinterpret_cast<const uint32_t*>(X + o_pc);
-    J.ids = reinterpret_cast<const uint32_t*>(X + o_id);
-    J.hsig = reinterpret_cast<const uint32_t*>(X + o_hs);
-    if (kind == nw::kSmallCerts) {
-      J.vpk = reinterpret_cast<const uint32_t*>(X + o_vp);
-      J.vsig = reinterpret_cast<const uint32_t*>(X + o_vs);
-      J.z16 = z16 ? reinterpret_cast<const uint32_t*>(X + o_z) : nullptr;
-    }
-  }
+  nw_certificates dcs = stg::view_headers(X, oh, n, hlen);
+  const uint8_t* dz = stg::view_cert_votes(X, ov, nv, &dcs);
+  small_inputs(J, stg::view_committee(X, oc, na), dcs, dz, stg::view_vote_msgs(X, om, n));
   J.slots = reinterpret_cast<const nw::small_slot_t*>(X + o_sl);
   J.bcomb = bcomb;
   if (!z16) {
@@ -1071,54 +1020,27 @@ int submit_certs(int dev, const nw_committee* com, const nw_certificates* cs, in
     *job = j;
     return 0;
   }
-  const uint64_t hb0 = cs->header_offsets[0], hlen = cs->header_offsets[n] - hb0;
+  const uint64_t hlen = cs->header_offsets[n] - cs->header_offsets[0];
   Packer P;
-  const CommitteeOffs oc = plan_committee(P, com);
-  const size_t o_hb = P.add(hlen), o_ho = P.add(8 * (n + 1)), o_pc = P.add(4 * n),
-               o_id = P.add(32 * n), o_hs = P.add(64 * n);
-  size_t o_vo = 0, o_vp = 0, o_vs = 0, o_z = 0;
-  if (!headers_only) {
-    o_vo = P.add(8 * (n + 1));
-    o_vp = P.add(32 * nv);
-    o_vs = P.add(64 * nv);
-    if (z16) o_z = P.add(16 * nv);
-  }
+  const stg::CommitteeOffs oc = stg::plan_committee(P, com);
+  const stg::HeaderOffs oh = stg::plan_headers(P, n, hlen);
+  stg::CertVoteOffs ov;
+  if (!headers_only) ov = stg::plan_cert_votes(P, n, nv, true, z16 != nullptr);
   const size_t o_st = P.add(4 * n), o_ix = P.add(8 * n), out_end = P.off;
   const size_t o_ws = P.add(nw::rt::cert_workspace_bytes(n, nv));
   rc = job_reserve(j, out_end, P.off);
   if (rc) return job_abort(j, rc);
-  const nw_committee dcom = stage_committee(j, oc, com);
+  stg::fill_committee(j->hbuf, oc, com);
+  stg::fill_headers(j->hbuf, oh, cs);
+  if (!headers_only) stg::fill_cert_votes(j->hbuf, ov, cs, z16);
+  const nw_committee dcom = stg::view_committee(j->dbuf, oc, com->nauth);
   const uint64_t ctag = nw::rt::committee_hash(com);
-  put(j, o_hb, cs->header_bytes + hb0, hlen);
-  uint64_t* ho = reinterpret_cast<uint64_t*>(j->hbuf + o_ho);
-  for (size_t i = 0; i <= n; ++i) ho[i] = cs->header_offsets[i] - hb0;
-  put(j, o_pc, cs->payload_counts, 4 * n);
-  put(j, o_id, cs->ids, 32 * n);
-  put(j, o_hs, cs->header_sigs, 64 * n);
-  nw_certificates d{};
-  d.n = n;
-  d.header_bytes = reinterpret_cast<const uint8_t*>(j->dbuf + o_hb);
-  d.header_offsets = reinterpret_cast<const uint64_t*>(j->dbuf + o_ho);
-  d.payload_counts = reinterpret_cast<const uint32_t*>(j->dbuf + o_pc);
-  d.ids = reinterpret_cast<const uint8_t*>(j->dbuf + o_id);
-  d.header_sigs = reinterpret_cast<const uint8_t*>(j->dbuf + o_hs);
-  d.header_bytes_len = hlen;
-  const uint64_t* hvo = nullptr;
-  if (!headers_only) {
-    put(j, o_vo, cs->vote_offsets, 8 * (n + 1));
-    put(j, o_vp, cs->vote_pks, 32 * nv);
-    put(j, o_vs, cs->vote_sigs, 64 * nv);
-    if (z16) put(j, o_z, z16, 16 * nv);
-    d.vote_offsets = reinterpret_cast<const uint64_t*>(j->dbuf + o_vo);
-    d.vote_pks = reinterpret_cast<const uint8_t*>(j->dbuf + o_vp);
-    d.vote_sigs = reinterpret_cast<const uint8_t*>(j->dbuf + o_vs);
-    d.nvotes = nv;
-    hvo = reinterpret_cast<const uint64_t*>(j->hbuf + o_vo);   // read while planning only
-  }
+  nw_certificates d = stg::view_headers(j->dbuf, oh, n, hlen);
+  const uint8_t* dz = stg::view_cert_votes(j->dbuf, ov, nv, &d);
+  const uint64_t* hvo = stg::at<uint64_t>(j->hbuf, ov.vo);   // read while planning only
   if (!headers_only) ensure_fork(j);
   rc = job_run(j, o_st, o_st, out_end - o_st, [&]() -> int {
-    return nw::rt::cert_pipeline(dev, dcom, d, hvo, headers_only, z16 ? j->dbuf + o_z : nullptr,
-                                 nullptr, j->dbuf + o_ws,
+    return nw::rt::cert_pipeline(dev, dcom, d, hvo, headers_only, dz, nullptr, j->dbuf + o_ws,
                                  reinterpret_cast<int32_t*>(j->dbuf + o_st),
                                  reinterpret_cast<uint64_t*>(j->dbuf + o_ix), j->stream, ctag,
                                  j->fork.s2 ? &j->fork : nullptr, com->pks);
@@ -1139,8 +1061,8 @@ int submit_votes(int dev, const nw_committee* com, const uint8_t* ids, const uin
   if (rc) return rc;
   if (n && (!ids || !rounds || !origins || !authors || !sigs || !status_out))
     return set_err(NW_E_INVALID_ARG, "null pointer");
+  const stg::VoteMsgs va{ids, rounds, origins, authors, sigs, n};
   if (n) {   // a small job: one launch (nw_small.hip), when it qualifies
-    const VoteArrays va{ids, origins, authors, sigs, rounds, n};
     rc = submit_small(dev, nw::kSmallVotes, com, nullptr, &va, nullptr, status_out, nullptr, job);
     if (rc <= 0) return rc;
     g_pipeline_jobs.fetch_add(1, std::memory_order_relaxed);
@@ -1153,26 +1075,20 @@ int submit_votes(int dev, const nw_committee* com, const uint8_t* ids, const uin
     return 0;
   }
   Packer P;
-  const CommitteeOffs oc = plan_committee(P, com);
-  const size_t o_id = P.add(32 * n), o_rd = P.add(8 * n), o_or = P.add(32 * n),
-               o_au = P.add(32 * n), o_sg = P.add(64 * n);
+  const stg::CommitteeOffs oc = stg::plan_committee(P, com);
+  const stg::VoteMsgOffs om = stg::plan_vote_msgs(P, n);
   const size_t o_st = P.add(4 * n), out_end = P.off;
   const size_t o_ws = P.add(nw::rt::votes_workspace_bytes(n));
   rc = job_reserve(j, out_end, P.off);
   if (rc) return job_abort(j, rc);
-  const nw_committee dcom = stage_committee(j, oc, com);
-  put(j, o_id, ids, 32 * n);
-  put(j, o_rd, rounds, 8 * n);
-  put(j, o_or, origins, 32 * n);
-  put(j, o_au, authors, 32 * n);
-  put(j, o_sg, sigs, 64 * n);
+  stg::fill_committee(j->hbuf, oc, com);
+  stg::fill_vote_msgs(j->hbuf, om, va);
+  const nw_committee dcom = stg::view_committee(j->dbuf, oc, com->nauth);
+  const stg::VoteMsgs d = stg::view_vote_msgs(j->dbuf, om, n);
   rc = job_run(j, o_st, o_st, out_end - o_st, [&]() -> int {
-    const auto* b = reinterpret_cast<const uint8_t*>(j->dbuf);
-    return nw::rt::votes_pipeline(dev, dcom, n, b + o_id,
-                                  reinterpret_cast<const uint64_t*>(b + o_rd), b + o_or,
-                                  b + o_au, b + o_sg, j->dbuf + o_ws,
-                                  reinterpret_cast<int32_t*>(j->dbuf + o_st), j->stream,
-                                  com->pks);
+    return nw::rt::votes_pipeline(dev, dcom, n, d.ids, d.rounds, d.origins, d.authors, d.sigs,
+                                  j->dbuf + o_ws, reinterpret_cast<int32_t*>(j->dbuf + o_st),
+                                  j->stream, com->pks);
   });
   if (rc) return job_abort(j, rc);
   job_out(j, status_out, o_st, 4 * n);
@@ -1223,49 +1139,64 @@ std::vector<size_t> weighted_bounds(size_t n, size_t P, const std::vector<uint64
   return b;
 }
 
+// The frame of every nw_submit_*: *job cleared, the call's own argument checks (0 = fine),
+// then one(dev) on the thread's device, or (NW_ALL_DEVICES) many(devs), the call's fan-out.
+template <class Check, class One, class Many>
+int submit_entry(nw_job** job, Check check, One one, Many many) {
+  if (!job) return set_err(NW_E_INVALID_ARG, "null job pointer");
+  *job = nullptr;
+  int rc = check();
+  if (rc) return rc;
+  const std::vector<int> devs = nw::rt::fanout_devices();
+  if (!devs.empty()) return many(devs);
+  int dev = 0;
+  rc = nw::rt::select_device(&dev);
+  return rc ? rc : one(dev);
+}
+
 // Header / Certificate submits: one device, or whole messages per device with about equal
 // work (1 per header + 1 per vote).
 int submit_messages(const nw_committee* com, const nw_certificates* cs, int headers_only,
                     const uint8_t* z16, int32_t* status_out, uint64_t* index_out,
                     nw_job** job) {
-  const std::vector<int> devs = nw::rt::fanout_devices();
-  if (devs.empty()) {
-    int dev = 0;
-    int rc = nw::rt::select_device(&dev);
-    return rc ? rc : submit_certs(dev, com, cs, headers_only, z16, status_out, index_out, job);
-  }
-  size_t nv = 0;
-  int rc = nw::rt::check_committee(com);
-  if (!rc) rc = nw::rt::check_certificates(cs, headers_only, &nv);
-  if (rc) return rc;
-  const size_t n = cs->n;
-  std::vector<uint64_t> w(n + 1, 0);
-  for (size_t i = 0; i < n; ++i)
-    w[i + 1] = w[i] + 1 + (headers_only ? 0 : cs->vote_offsets[i + 1] - cs->vote_offsets[i]);
-  return fan_out(devs, weighted_bounds(n, devs.size(), w),
-                 [&](int dev, size_t a, size_t e, nw_job** sub) {
-                   nw_certificates part = *cs;
-                   part.n = e - a;
-                   part.header_offsets = cs->header_offsets + a;   // absolute: rebased
-                   part.payload_counts = cs->payload_counts + a;
-                   part.ids = cs->ids + 32 * a;
-                   part.header_sigs = cs->header_sigs + 64 * a;
-                   std::vector<uint64_t> vo;
-                   const uint8_t* pz = z16;
-                   if (!headers_only) {
-                     const uint64_t v0 = cs->vote_offsets[a];
-                     vo.resize(e - a + 1);
-                     for (size_t i = a; i <= e; ++i) vo[i - a] = cs->vote_offsets[i] - v0;
-                     part.vote_offsets = vo.data();   // copied into the part's staging
-                     part.vote_pks = cs->vote_pks ? cs->vote_pks + 32 * v0 : nullptr;
-                     part.vote_sigs = cs->vote_sigs ? cs->vote_sigs + 64 * v0 : nullptr;
-                     if (z16) pz = z16 + 16 * v0;
-                   }
-                   return submit_certs(dev, com, &part, headers_only, pz,
-                                       status_out ? status_out + a : nullptr,
-                                       index_out ? index_out + a : nullptr, sub);
-                 },
-                 job);
+  const auto one = [&](int dev) {
+    return submit_certs(dev, com, cs, headers_only, z16, status_out, index_out, job);
+  };
+  const auto many = [&](const std::vector<int>& devs) -> int {
+    size_t nv = 0;
+    int rc = nw::rt::check_committee(com);
+    if (!rc) rc = nw::rt::check_certificates(cs, headers_only, &nv);
+    if (rc) return rc;
+    const size_t n = cs->n;
+    std::vector<uint64_t> w(n + 1, 0);
+    for (size_t i = 0; i < n; ++i)
+      w[i + 1] = w[i] + 1 + (headers_only ? 0 : cs->vote_offsets[i + 1] - cs->vote_offsets[i]);
+    return fan_out(devs, weighted_bounds(n, devs.size(), w),
+                   [&](int dev, size_t a, size_t e, nw_job** sub) {
+                     nw_certificates part = *cs;
+                     part.n = e - a;
+                     part.header_offsets = cs->header_offsets + a;   // absolute: rebased
+                     part.payload_counts = cs->payload_counts + a;
+                     part.ids = cs->ids + 32 * a;
+                     part.header_sigs = cs->header_sigs + 64 * a;
+                     std::vector<uint64_t> vo;
+                     const uint8_t* pz = z16;
+                     if (!headers_only) {
+                       const uint64_t v0 = cs->vote_offsets[a];
+                       vo.resize(e - a + 1);
+                       for (size_t i = a; i <= e; ++i) vo[i - a] = cs->vote_offsets[i] - v0;
+                       part.vote_offsets = vo.data();   // copied into the part's staging
+                       part.vote_pks = cs->vote_pks ? cs->vote_pks + 32 * v0 : nullptr;
+                       part.vote_sigs = cs->vote_sigs ? cs->vote_sigs + 64 * v0 : nullptr;
+                       if (z16) pz = z16 + 16 * v0;
+                     }
+                     return submit_certs(dev, com, &part, headers_only, pz,
+                                         status_out ? status_out + a : nullptr,
+                                         index_out ? index_out + a : nullptr, sub);
+                   },
+                   job);
+  };
+  return submit_entry(job, [] { return 0; }, one, many);
 }
 
 // ---- wire ingest, decoded on the device -------------------------------------------------
@@ -1274,48 +1205,29 @@ int submit_messages(const nw_committee* com, const nw_certificates* cs, int head
 // one frame, so the cap keeps an adversarial multi-megabyte frame from serialising a lane;
 // longer frames are the host decoder's.
 uint64_t wire_max_frame() {
-  static const uint64_t v = [] {
-    const char* e = getenv("NW_WIRE_MAX_FRAME");
-    const long long x = e && *e ? atoll(e) : 0;
-    return x > 0 ? (uint64_t)std::min<long long>(x, 1ll << 30) : (uint64_t)32768;
-  }();
-  return v;
+  static const long long x = env_int("NW_WIRE_MAX_FRAME", 0);
+  return x > 0 ? (uint64_t)std::min<long long>(x, 1ll << 30) : (uint64_t)32768;
 }
 // Lanes per frame of the emit: 16, or a whole wave once the frames are large (a certificate
 // of a 100-member committee is ~10 KB, ~2,400 word tasks). NW_WIRE_EMIT_GROUP=16|64: A/B hook.
 uint32_t wire_emit_group(uint64_t total, uint64_t n) {
-  static const int fixed = [] {
-    const char* e = getenv("NW_WIRE_EMIT_GROUP");
-    const int g = e && *e ? atoi(e) : 0;
-    return g == 16 || g == 64 ? g : 0;
-  }();
-  if (fixed) return (uint32_t)fixed;
+  static const int fixed = (int)env_int("NW_WIRE_EMIT_GROUP", 0);
+  if (fixed == 16 || fixed == 64) return (uint32_t)fixed;
   return total / n >= 2048 ? 64u : 16u;
 }
 // Lanes per frame of the canonicalisation: a wave, or four once the frames are large (its walks
 // are quadratic in a frame's entries). NW_WIRE_CANON_LANES=64|256: A/B hook.
 uint32_t wire_canon_lanes(uint64_t total, uint64_t n) {
-  static const int fixed = [] {
-    const char* e = getenv("NW_WIRE_CANON_LANES");
-    const int g = e && *e ? atoi(e) : 0;
-    return g == 64 || g == 256 ? g : 0;
-  }();
-  if (fixed) return (uint32_t)fixed;
+  static const int fixed = (int)env_int("NW_WIRE_CANON_LANES", 0);
+  if (fixed == 64 || fixed == 256) return (uint32_t)fixed;
   return total / n >= 2048 ? 256u : 64u;
 }
 unsigned wire_stage_threads() {   // NW_WIRE_STAGE_THREADS=0..8 (default 4; 0: the caller stages)
-  static const unsigned v = [] {
-    const char* e = getenv("NW_WIRE_STAGE_THREADS");
-    const int x = e && *e ? atoi(e) : 4;
-    return (unsigned)std::min(std::max(x, 0), 8);
-  }();
-  return v;
+  static const int x = (int)env_int("NW_WIRE_STAGE_THREADS", 4);
+  return (unsigned)std::min(std::max(x, 0), 8);
 }
 bool wire_stamps() {   // NW_WIRE_STAMPS=1: per-phase host times of every device-decode call
-  static const bool on = [] {
-    const char* e = getenv("NW_WIRE_STAMPS");
-    return e && *e == '1';
-  }();
+  static const bool on = env_flag("NW_WIRE_STAMPS", false);
   return on;
 }
 
@@ -1369,7 +1281,7 @@ int nw::rt::wire_verify_device(int dev, const nw_committee* com, const uint8_t* 
   if (rc) return rc;
   Packer P;
   const size_t o_fr = P.add(total + 4), o_of = P.add(8 * (n + 1));
-  const CommitteeOffs oc = plan_committee(P, com);
+  const stg::CommitteeOffs oc = stg::plan_committee(P, com);
   const size_t in_end = P.off;
   const size_t o_rec = P.add(sizeof(wd::rec_t) * n);
   const size_t o_can = canon ? P.add(sizeof(wd::canon_t) * n) : 0;   // (behind the records)
@@ -1395,7 +1307,8 @@ int nw::rt::wire_verify_device(int dev, const nw_committee* com, const uint8_t* 
     ho[i] = offsets[i] - base0;
     if (i) maxlen = std::max(maxlen, ho[i] - ho[i - 1]);
   }
-  const nw_committee dcom = stage_committee(j, oc, com);
+  stg::fill_committee(H, oc, com);
+  const nw_committee dcom = stg::view_committee(D, oc, com->nauth);
   const uint64_t ctag = nw::rt::committee_hash(com);
   memset(H + o_fr + total, 0, 4);
   // Staging: 2 MiB chunks, each copied up as soon as it is in the pinned buffer. From 8 MiB
@@ -1466,28 +1379,16 @@ int nw::rt::wire_verify_device(int dev, const nw_committee* com, const uint8_t* 
                               kind_out, status_out, index_out);
   if (bad) return job_abort(j, set_err(NW_E_DEVICE, bad));
   const uint64_t nh = pl.cnt[0], nc = pl.cnt[1];
+  // the structure-of-arrays: the staged groups' layout (nw_stage.hpp), device only; the emit
+  // writes it and the pipelines read it through the same views
   Packer S;
   S.off = o_soa;
-  wd::out_t out{};
-  for (int k = 0; k < 2; ++k) {
-    out.hb[k] = reinterpret_cast<uint8_t*>(D + S.add(pl.hbl[k]));
-    out.hb_len[k] = pl.hbl[k];
-    out.ho[k] = reinterpret_cast<uint64_t*>(D + S.add(8 * (pl.cnt[k] + 1)));
-    out.pc[k] = reinterpret_cast<uint32_t*>(D + S.add(4 * pl.cnt[k]));
-    out.ids[k] = reinterpret_cast<uint32_t*>(D + S.add(32 * pl.cnt[k]));
-    out.sigs[k] = reinterpret_cast<uint32_t*>(D + S.add(64 * pl.cnt[k]));
-    out.nitems[k] = (uint32_t)pl.cnt[k];
-  }
-  out.vo = reinterpret_cast<uint64_t*>(D + S.add(8 * (nc + 1)));
-  out.vpk = reinterpret_cast<uint32_t*>(D + S.add(32 * pl.nvotes));
-  out.vsig = reinterpret_cast<uint32_t*>(D + S.add(64 * pl.nvotes));
-  out.nvotes = (uint32_t)pl.nvotes;
-  out.v_ids = reinterpret_cast<uint32_t*>(D + S.add(32 * pl.nvm));
-  out.v_rounds = reinterpret_cast<uint64_t*>(D + S.add(8 * pl.nvm));
-  out.v_origins = reinterpret_cast<uint32_t*>(D + S.add(32 * pl.nvm));
-  out.v_authors = reinterpret_cast<uint32_t*>(D + S.add(32 * pl.nvm));
-  out.v_sigs = reinterpret_cast<uint32_t*>(D + S.add(64 * pl.nvm));
-  out.nvmsg = (uint32_t)pl.nvm;
+  nw_certificates d[2];
+  for (int k = 0; k < 2; ++k)
+    d[k] = stg::view_headers(D, stg::plan_headers(S, pl.cnt[k], pl.hbl[k]), pl.cnt[k], pl.hbl[k]);
+  stg::view_cert_votes(D, stg::plan_cert_votes(S, nc, pl.nvotes, true, false), pl.nvotes, &d[1]);
+  const stg::VoteMsgs vm = stg::view_vote_msgs(D, stg::plan_vote_msgs(S, pl.nvm), pl.nvm);
+  const wd::out_t out = wire_out(d, vm);
   const size_t ws_need = std::max({nw::rt::cert_workspace_bytes(nh, 0),
                                    nw::rt::cert_workspace_bytes(nc, pl.nvotes),
                                    nw::rt::votes_workspace_bytes(pl.nvm)});
@@ -1507,30 +1408,13 @@ int nw::rt::wire_verify_device(int dev, const nw_committee* com, const uint8_t* 
     uint64_t* dst_ix = reinterpret_cast<uint64_t*>(D + o_ix);
     for (int k = 0; k < 2 && !rc; ++k) {
       if (!pl.cnt[k]) continue;
-      nw_certificates d{};
-      d.n = pl.cnt[k];
-      d.header_bytes = out.hb[k];
-      d.header_offsets = out.ho[k];
-      d.payload_counts = out.pc[k];
-      d.ids = reinterpret_cast<const uint8_t*>(out.ids[k]);
-      d.header_sigs = reinterpret_cast<const uint8_t*>(out.sigs[k]);
-      d.header_bytes_len = pl.hbl[k];
-      if (k) {
-        d.vote_offsets = out.vo;
-        d.vote_pks = reinterpret_cast<const uint8_t*>(out.vpk);
-        d.vote_sigs = reinterpret_cast<const uint8_t*>(out.vsig);
-        d.nvotes = pl.nvotes;
-      }
-      rc = nw::rt::cert_pipeline(dev, dcom, d, k ? cvo.data() : nullptr, !k, nullptr, nullptr,
+      rc = nw::rt::cert_pipeline(dev, dcom, d[k], k ? cvo.data() : nullptr, !k, nullptr, nullptr,
                                  D + o_ws, dst_st + (k ? nh : 0), dst_ix + (k ? nh : 0),
                                  j->stream, ctag, nullptr, com->pks);
     }
     if (!rc && pl.nvm)
-      rc = nw::rt::votes_pipeline(dev, dcom, pl.nvm, reinterpret_cast<const uint8_t*>(out.v_ids),
-                                  out.v_rounds, reinterpret_cast<const uint8_t*>(out.v_origins),
-                                  reinterpret_cast<const uint8_t*>(out.v_authors),
-                                  reinterpret_cast<const uint8_t*>(out.v_sigs), D + o_ws,
-                                  dst_st + nh + nc, j->stream, com->pks);
+      rc = nw::rt::votes_pipeline(dev, dcom, pl.nvm, vm.ids, vm.rounds, vm.origins, vm.authors,
+                                  vm.sigs, D + o_ws, dst_st + nh + nc, j->stream, com->pks);
     if (rc) return job_abort(j, rc);
     // 5. verdicts
     e = hipMemcpyAsync(H + o_st, D + o_st, 4 * nitems, hipMemcpyDeviceToHost, j->stream);
@@ -1569,101 +1453,96 @@ extern "C" {
 int nw_submit_verify_strict(const uint8_t* digests, size_t digest_stride, const uint8_t* pks,
                             const uint8_t* sigs, size_t n, int32_t* status_out,
                             uint8_t* bitmap_out, nw_job** job) {
-  if (!job) return set_err(NW_E_INVALID_ARG, "null job pointer");
-  *job = nullptr;
-  if (n && (!digests || !pks || !sigs)) return set_err(NW_E_INVALID_ARG, "null pointer");
-  if (digest_stride != 0 && digest_stride != 32)
-    return set_err(NW_E_INVALID_ARG, "digest_stride must be 0 or 32");
-  const std::vector<int> devs = nw::rt::fanout_devices();
-  if (devs.empty()) {
-    int dev = 0;
-    int rc = nw::rt::select_device(&dev);
-    return rc ? rc : submit_strict(dev, digests, digest_stride, pks, sigs, n, status_out,
-                                   bitmap_out, job);
-  }
-  return fan_out(devs, even_bounds(n, devs.size(), 64),
-                 [&](int dev, size_t a, size_t e, nw_job** sub) {
-                   return submit_strict(dev, digests + (digest_stride ? 32 * a : 0),
-                                        digest_stride, pks + 32 * a, sigs + 64 * a, e - a,
-                                        status_out ? status_out + a : nullptr,
-                                        bitmap_out ? bitmap_out + a / 8 : nullptr, sub);
-                 },
-                 job);
+  const auto check = [&]() -> int {
+    if (n && (!digests || !pks || !sigs)) return set_err(NW_E_INVALID_ARG, "null pointer");
+    if (digest_stride != 0 && digest_stride != 32)
+      return set_err(NW_E_INVALID_ARG, "digest_stride must be 0 or 32");
+    return 0;
+  };
+  const auto one = [&](int dev) {
+    return submit_strict(dev, digests, digest_stride, pks, sigs, n, status_out, bitmap_out, job);
+  };
+  const auto many = [&](const std::vector<int>& devs) {
+    return fan_out(devs, even_bounds(n, devs.size(), 64),
+                   [&](int dev, size_t a, size_t e, nw_job** sub) {
+                     return submit_strict(dev, digests + (digest_stride ? 32 * a : 0),
+                                          digest_stride, pks + 32 * a, sigs + 64 * a, e - a,
+                                          status_out ? status_out + a : nullptr,
+                                          bitmap_out ? bitmap_out + a / 8 : nullptr, sub);
+                   },
+                   job);
+  };
+  return submit_entry(job, check, one, many);
 }
 
 int nw_submit_verify_batch_many(const uint8_t* digests, const uint8_t* pks, const uint8_t* sigs,
                                 const uint64_t* offsets, size_t nbatches, const uint8_t* z16,
                                 int32_t* status_out, uint64_t* fail_index_out, nw_job** job) {
-  if (!job) return set_err(NW_E_INVALID_ARG, "null job pointer");
-  *job = nullptr;
-  if (nbatches && (!digests || !offsets)) return set_err(NW_E_INVALID_ARG, "null pointer");
-  if (nbatches) {
-    if (offsets[0] != 0) return set_err(NW_E_INVALID_ARG, "offsets[0] must be 0");
-    for (size_t b = 0; b < nbatches; ++b)
-      if (offsets[b + 1] < offsets[b]) return set_err(NW_E_INVALID_ARG, "offsets not monotone");
-  }
-  const size_t nitems = nbatches ? offsets[nbatches] : 0;
-  if (nitems && (!pks || !sigs)) return set_err(NW_E_INVALID_ARG, "null pointer");
-  const std::vector<int> devs = nw::rt::fanout_devices();
-  if (devs.empty()) {
-    int dev = 0;
-    int rc = nw::rt::select_device(&dev);
-    return rc ? rc : submit_batch(dev, digests, pks, sigs, offsets, nbatches, z16, status_out,
-                                  fail_index_out, job);
-  }
-  // whole batches per part, about equal votes (+1 per batch for its fixed tail)
-  std::vector<uint64_t> w(nbatches + 1);
-  for (size_t b = 0; b <= nbatches; ++b) w[b] = offsets[b] + b;
-  return fan_out(devs, weighted_bounds(nbatches, devs.size(), w),
-                 [&](int dev, size_t a, size_t e, nw_job** sub) {
-                   std::vector<uint64_t> off(e - a + 1);
-                   for (size_t b = a; b <= e; ++b) off[b - a] = offsets[b] - offsets[a];
-                   const uint64_t v0 = offsets[a];
-                   return submit_batch(dev, digests + 32 * a, pks ? pks + 32 * v0 : nullptr,
-                                       sigs ? sigs + 64 * v0 : nullptr, off.data(), e - a,
-                                       z16 ? z16 + 16 * v0 : nullptr,
-                                       status_out ? status_out + a : nullptr,
-                                       fail_index_out ? fail_index_out + a : nullptr, sub);
-                 },
-                 job);
+  const auto check = [&]() -> int {
+    if (nbatches && (!digests || !offsets)) return set_err(NW_E_INVALID_ARG, "null pointer");
+    if (nbatches) {
+      if (offsets[0] != 0) return set_err(NW_E_INVALID_ARG, "offsets[0] must be 0");
+      for (size_t b = 0; b < nbatches; ++b)
+        if (offsets[b + 1] < offsets[b]) return set_err(NW_E_INVALID_ARG, "offsets not monotone");
+    }
+    const size_t nitems = nbatches ? offsets[nbatches] : 0;
+    if (nitems && (!pks || !sigs)) return set_err(NW_E_INVALID_ARG, "null pointer");
+    return 0;
+  };
+  const auto one = [&](int dev) {
+    return submit_batch(dev, digests, pks, sigs, offsets, nbatches, z16, status_out,
+                        fail_index_out, job);
+  };
+  const auto many = [&](const std::vector<int>& devs) {
+    // whole batches per part, about equal votes (+1 per batch for its fixed tail)
+    std::vector<uint64_t> w(nbatches + 1);
+    for (size_t b = 0; b <= nbatches; ++b) w[b] = offsets[b] + b;
+    return fan_out(devs, weighted_bounds(nbatches, devs.size(), w),
+                   [&](int dev, size_t a, size_t e, nw_job** sub) {
+                     std::vector<uint64_t> off(e - a + 1);
+                     for (size_t b = a; b <= e; ++b) off[b - a] = offsets[b] - offsets[a];
+                     const uint64_t v0 = offsets[a];
+                     return submit_batch(dev, digests + 32 * a, pks ? pks + 32 * v0 : nullptr,
+                                         sigs ? sigs + 64 * v0 : nullptr, off.data(), e - a,
+                                         z16 ? z16 + 16 * v0 : nullptr,
+                                         status_out ? status_out + a : nullptr,
+                                         fail_index_out ? fail_index_out + a : nullptr, sub);
+                   },
+                   job);
+  };
+  return submit_entry(job, check, one, many);
 }
 
 int nw_submit_sha512_digest32_many(const uint8_t* data, const uint64_t* offsets,
                                    const uint64_t* lengths, size_t n, uint8_t* out32,
                                    nw_job** job) {
-  if (!job) return set_err(NW_E_INVALID_ARG, "null job pointer");
-  *job = nullptr;
-  if (n && (!data || !offsets || !lengths || !out32))
-    return set_err(NW_E_INVALID_ARG, "null pointer");
-  const std::vector<int> devs = nw::rt::fanout_devices();
-  if (devs.empty()) {
-    int dev = 0;
-    int rc = nw::rt::select_device(&dev);
-    return rc ? rc : submit_sha(dev, data, offsets, lengths, n, out32, job);
-  }
-  // whole messages per part, about equal bytes (+1 per message)
-  std::vector<uint64_t> w(n + 1, 0);
-  for (size_t i = 0; i < n; ++i) w[i + 1] = w[i] + lengths[i] + 1;
-  return fan_out(devs, weighted_bounds(n, devs.size(), w),
-                 [&](int dev, size_t a, size_t e, nw_job** sub) {
-                   return submit_sha(dev, data, offsets + a, lengths + a, e - a, out32 + 32 * a,
-                                     sub);
-                 },
-                 job);
+  const auto check = [&] {
+    const bool bad = n && (!data || !offsets || !lengths || !out32);
+    return bad ? set_err(NW_E_INVALID_ARG, "null pointer") : 0;
+  };
+  const auto one = [&](int dev) { return submit_sha(dev, data, offsets, lengths, n, out32, job); };
+  const auto many = [&](const std::vector<int>& devs) {
+    // whole messages per part, about equal bytes (+1 per message)
+    std::vector<uint64_t> w(n + 1, 0);
+    for (size_t i = 0; i < n; ++i) w[i + 1] = w[i] + lengths[i] + 1;
+    return fan_out(devs, weighted_bounds(n, devs.size(), w),
+                   [&](int dev, size_t a, size_t e, nw_job** sub) {
+                     return submit_sha(dev, data, offsets + a, lengths + a, e - a,
+                                       out32 + 32 * a, sub);
+                   },
+                   job);
+  };
+  return submit_entry(job, check, one, many);
 }
 
 int nw_submit_certificates_verify_many(const nw_committee* committee,
                                        const nw_certificates* certs, const uint8_t* z16,
                                        int32_t* status_out, uint64_t* index_out, nw_job** job) {
-  if (!job) return set_err(NW_E_INVALID_ARG, "null job pointer");
-  *job = nullptr;
   return submit_messages(committee, certs, 0, z16, status_out, index_out, job);
 }
 
 int nw_submit_headers_verify_many(const nw_committee* committee, const nw_certificates* headers,
                                   int32_t* status_out, uint64_t* index_out, nw_job** job) {
-  if (!job) return set_err(NW_E_INVALID_ARG, "null job pointer");
-  *job = nullptr;
   return submit_messages(committee, headers, 1, nullptr, status_out, index_out, job);
 }
 
@@ -1671,26 +1550,25 @@ int nw_submit_votes_verify_many(const nw_committee* committee, const uint8_t* id
                                 const uint64_t* rounds, const uint8_t* origins,
                                 const uint8_t* authors, const uint8_t* sigs, size_t n,
                                 int32_t* status_out, nw_job** job) {
-  if (!job) return set_err(NW_E_INVALID_ARG, "null job pointer");
-  *job = nullptr;
-  if (n && (!ids || !rounds || !origins || !authors || !sigs || !status_out))
-    return set_err(NW_E_INVALID_ARG, "null pointer");
-  const std::vector<int> devs = nw::rt::fanout_devices();
-  if (devs.empty()) {
-    int dev = 0;
-    int rc = nw::rt::select_device(&dev);
-    return rc ? rc : submit_votes(dev, committee, ids, rounds, origins, authors, sigs, n,
-                                  status_out, job);
-  }
-  int rc = nw::rt::check_committee(committee);
-  if (rc) return rc;
-  return fan_out(devs, even_bounds(n, devs.size(), 1),
-                 [&](int dev, size_t a, size_t e, nw_job** sub) {
-                   return submit_votes(dev, committee, ids + 32 * a, rounds + a, origins + 32 * a,
-                                       authors + 32 * a, sigs + 64 * a, e - a, status_out + a,
-                                       sub);
-                 },
-                 job);
+  const auto check = [&] {
+    const bool bad = n && (!ids || !rounds || !origins || !authors || !sigs || !status_out);
+    return bad ? set_err(NW_E_INVALID_ARG, "null pointer") : 0;
+  };
+  const auto one = [&](int dev) {
+    return submit_votes(dev, committee, ids, rounds, origins, authors, sigs, n, status_out, job);
+  };
+  const auto many = [&](const std::vector<int>& devs) -> int {
+    int rc = nw::rt::check_committee(committee);
+    if (rc) return rc;
+    return fan_out(devs, even_bounds(n, devs.size(), 1),
+                   [&](int dev, size_t a, size_t e, nw_job** sub) {
+                     return submit_votes(dev, committee, ids + 32 * a, rounds + a,
+                                         origins + 32 * a, authors + 32 * a, sigs + 64 * a, e - a,
+                                         status_out + a, sub);
+                   },
+                   job);
+  };
+  return submit_entry(job, check, one, many);
 }
 
 int nw_job_poll(nw_job* job) {

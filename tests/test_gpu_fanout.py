@@ -102,6 +102,34 @@ def test_fanout_messages_vs_oracle(fanout):
     assert M.verify_votes_many(_Com(vcom), p).tolist() == exp.tolist()
 
 
+def test_fanout_parts_as_small_jobs(monkeypatch):
+    """Three parts, each a small job: every part after the first has header_offsets[0] != 0
+    (and rebased vote offsets, its slice of z16), which the staging rebases to 0. The second
+    run of each call is small-job launches only (the first builds the committee's tables)."""
+    L = _lib.lib()
+    assert L.nw_init() > 0
+    monkeypatch.setenv("NW_FANOUT_PARTS", "3")
+    monkeypatch.setenv("NW_SMALL", "1")
+    com, s, _, _, _ = mutated_stream(N=4, copies=3, seed=43)
+    z16 = np.random.Generator(np.random.PCG64(43)).integers(0, 256, size=(len(s["vote_pks"]), 16),
+                                                            dtype=np.uint8)
+    assert L.nw_set_device(ALL) == 0
+    try:
+        for fn, ref in ((lambda: M.verify_certificates_many(_Com(com), s, z16),
+                         lambda: O.certificates_verify_many(com, s, z16)),
+                        (lambda: M.verify_headers_many(_Com(com), s),
+                         lambda: O.certificates_verify_many(com, s, headers_only=True))):
+            fn()
+            s0, p0 = _lib.path_stats()
+            st, ix = fn()
+            s1, p1 = _lib.path_stats()
+            assert s1 == s0 + 3 and p1 == p0, (s0, s1, p0, p1)
+            ost, oix = ref()
+            assert st.tolist() == ost.tolist() and ix.tolist() == oix.tolist()
+    finally:
+        assert L.nw_set_device(0) == 0
+
+
 def test_fanout_async_jobs_notify(fanout):
     """Parent jobs: poll until done, notify fires once after every part finished."""
     L = _lib.lib()
