@@ -84,6 +84,14 @@ stagesan: tools/stage_san
 tools/stage_san: tools/stagecheck.hip $(CSRC)/nw_stage.hpp include/narwhal_amd.h
 	g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -DSTAGECHECK_MAIN -Iinclude -x c++ $< -o $@
 
+# the key set's sizing, region planning and probe / build / triage / ladder sequence
+# (nw_kernels.h, nw_strict.hpp) under AddressSanitizer / UBSan, as a stand-alone CPU program
+# (not part of `all`; the instrumented field arithmetic takes about ten minutes to compile):
+# make keysetsan && tools/keyset_san
+keysetsan: tools/keyset_san
+tools/keyset_san: tools/hostcheck.hip $(HDRS)
+	$(HIPCC) --cuda-host-only -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -DKEYSET_SAN_MAIN -Iinclude $< -o $@
+
 loadgen: tools/libnw_loadgen.so
 tools/libnw_loadgen.so: tools/nw_loadgen.cpp include/narwhal_amd.h $(LIB)
 	g++ -O2 -std=c++17 -fPIC -shared -Iinclude $< -o $@ -Lnarwhal_amd -lnarwhal_amd -Wl,-rpath,'$$ORIGIN/../narwhal_amd' -pthread
@@ -102,7 +110,7 @@ tools/ubench_valu: tools/ubench_valu.hip
 	$(HIPCC) --offload-arch=$(ARCH) -O3 $< -o $@
 
 clean:
-	rm -rf $(BUILD) $(LIB) tools/libnw_hostcheck.so tools/libnw_wirecheck.so tools/libnw_stagecheck.so tools/libnw_loadgen.so tools/service_stress tools/service_stress_tsan tools/wire_canon_san tools/stage_san
+	rm -rf $(BUILD) $(LIB) tools/libnw_hostcheck.so tools/libnw_wirecheck.so tools/libnw_stagecheck.so tools/libnw_loadgen.so tools/service_stress tools/service_stress_tsan tools/wire_canon_san tools/stage_san tools/keyset_san
 	$(MAKE) -s -C oracle clean
 
-.PHONY: all oracle hostcheck wirecheck stagecheck wiresan stagesan loadgen stress ubench clean
+.PHONY: all oracle hostcheck wirecheck stagecheck wiresan stagesan keysetsan loadgen stress ubench clean

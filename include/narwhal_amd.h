@@ -209,6 +209,13 @@ void nw_job_release(nw_job* job);
 /* Diagnostics: Header / Vote / Certificate host-buffer jobs submitted so far by path, the
  * small-job launch (one kernel, no copies) and the bulk pipeline. Either pointer may be NULL. */
 int nw_path_stats(uint64_t* small_jobs, uint64_t* pipeline_jobs);
+/* Diagnostics (tests and tools; nothing on a timed path calls it) of the last
+ * nw_dev_verify_strict_many-style launch without committee tables queued on the calling
+ * thread's device: out[0] = distinct public keys decompressed and tabulated once for the call
+ * (summed over its slices), out[1] = items that read such a shared table, out[2] = items that
+ * decompressed and tabulated their own key (all of them under NW_STRICT_KEYS=0). Waits for
+ * `stream` (the launch's) first. All zero before the first such launch. */
+int nw_dev_strict_keyset_stats(uint64_t out[3], void* stream);
 
 /* ---- aggregation service: one request per message, coalesced into device jobs ------- */
 /* The front end a crypto-gpu crate puts behind the primary's per-message checks: Core

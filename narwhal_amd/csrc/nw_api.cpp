@@ -45,6 +45,7 @@ struct SharedDev {
   void* strict_ws = nullptr;   // per-lane tables of k_verify_strict (fixed size)
   void* triage_ws = nullptr;   // the two-pass path's slice (grow-only, nw::strict_triage_bytes)
   uint64_t triage_cap = 0;     // items
+  uint64_t triage_keys = 0;    // key-set slots the region holds (nw::strict_keys_slots)
   void* ktabs = nullptr;       // committee key tables (grow-only)
   uint32_t* kok = nullptr;
   size_t kcap = 0;             // keys
@@ -288,6 +289,15 @@ int nw_dev_verify_strict_many(const void* digests, size_t digest_stride, const v
                                   static_cast<uint64_t*>(bitmap_out), ws, s),
          "k_verify_strict launch");
   return lease.release();
+}
+
+int nw_dev_strict_keyset_stats(uint64_t out[3], void* stream) {
+  DevCtx* c;
+  int rc = begin(&c);
+  if (rc) return rc;
+  if (!out) return set_err(NW_E_INVALID_ARG, "null pointer");
+  NW_HIP(nw::strict_keyset_stats(out, pick_stream(stream, c)), "strict key set statistics");
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------
@@ -1074,26 +1084,36 @@ int Lease::strict_ws(nw::strict_ws_t* out, size_t n) {
   // the two-pass path's slice for n items: grown (at least doubled, up to the slice limit's
   // size) after every queued launch that uses the old one has finished
   const uint64_t slice = nw::strict_triage_slice(n);
-  if (n && slice > d.triage_cap) {
-    const uint64_t cap = std::max<uint64_t>(
-        slice, std::min<uint64_t>(2 * d.triage_cap, nw::strict_triage_slice(~0ull >> 8)));
+  // the slice's key set (NW_STRICT_KEYS, read here once per launch): its tables follow the
+  // planes in the same region, which also grows when a launch asks for more slots
+  const uint64_t kslots = n ? nw::strict_keys_slots(slice) : 0;
+  if (n && (slice > d.triage_cap || kslots > d.triage_keys)) {
+    const uint64_t cap = slice > d.triage_cap
+        ? std::max<uint64_t>(slice, std::min<uint64_t>(2 * d.triage_cap,
+                                                       nw::strict_triage_slice(~0ull >> 8)))
+        : d.triage_cap;
+    const uint64_t keys = std::max<uint64_t>({kslots, d.triage_keys, nw::strict_keys_slots(cap)});
     if (d.triage_ws) {
       if (d.last_valid) (void)hipEventSynchronize(d.last);
       (void)hipFree(d.triage_ws);
       d.triage_ws = nullptr;
       d.triage_cap = 0;
+      d.triage_keys = 0;
     }
-    hipError_t e = nw::table_malloc(&d.triage_ws, nw::strict_triage_bytes(cap));
+    hipError_t e = nw::table_malloc(&d.triage_ws, nw::strict_triage_bytes(cap, keys));
     if (e != hipSuccess) {
       d.triage_ws = nullptr;
       return ::set_err(NW_E_OUT_OF_MEMORY, "hipMalloc (strict triage slice)", e);
     }
     d.triage_cap = cap;
+    d.triage_keys = keys;
   }
   out->base = d.strict_ws;
   out->triage = d.triage_ws;
   out->triage_cap = d.triage_cap;
+  out->key_slots_cap = d.triage_keys;
   out->slice = n ? slice : 0;
+  out->key_slots = kslots;
   return 0;
 }
 

@@ -37,13 +37,60 @@ size_t strict_workspace_bytes();
 // (NW_TRIAGE_SLICE = items lowers it, e.g. to run a small input through several slices);
 // 0 when the two-pass path is off.
 uint64_t strict_triage_slice(uint64_t n);
-size_t strict_triage_bytes(uint64_t slice);
+// The slice's key set: the items of a slice share public keys, so each distinct key is
+// decompressed and tabulated once per slice into a table that lives for the call only.
+// strict_keys_slots(slice) = slots of its hash table for a slice of that many items, from
+// NW_STRICT_KEYS (read per launch; 0 = off); strict_keys_plan is the pure sizing rule.
+// Slots are clamped to [64, 2^20], rounded up to a power of two (default 2^16: 64 MB of
+// tables) and to no more than 4 x the slice's items (every key of the slice then fills at most
+// a quarter of them: short probe chains); at most half of them are filled.
+constexpr uint64_t kKeySlotsDefault = 1ull << 16, kKeySlotsMin = 64, kKeySlotsMax = 1ull << 20;
+inline uint64_t strict_keys_plan(uint64_t requested, uint64_t slice) {
+  if (requested == 0 || slice == 0) return 0;
+  uint64_t want = requested < kKeySlotsMin ? kKeySlotsMin
+                : requested > kKeySlotsMax ? kKeySlotsMax : requested;
+  const uint64_t fill = 4 * slice < kKeySlotsMin ? kKeySlotsMin : 4 * slice;
+  if (want > fill) want = fill;
+  uint64_t cap = kKeySlotsMin;
+  while (cap < want) cap <<= 1;
+  return cap;
+}
+uint64_t strict_keys_slots(uint64_t slice);
+// Byte offsets of the region's parts for a slice (a multiple of 64 items) and key_slots slots
+// (0: no key set): kTriagePlaneCount planes, the list and the key-slot plane (a word per item
+// each), a kTriageBlockBytes block (count, nkeys, the diagnostic counters: tabulated keys at
+// byte 8, kKeyStatLanes 64-bit counters of items with a slot from byte 1024, spread so that the
+// blocks of k_strict_keys_probe do not queue on one address), then the key set: slots and flags
+// (a word per slot each), 256 bytes of padding, and the tables (kKeyTabBytes per slot; 256-byte
+// aligned, since every term before them is a multiple of 256).
+constexpr uint64_t kTriagePlaneCount = 42, kKeyTabBytes = 1024, kTriageBlockBytes = 2048;
+constexpr uint32_t kKeyStatLanes = 128;
+struct strict_region_t {
+  uint64_t list, keyslot, block, slots, kflags, ktabs, bytes;
+};
+inline strict_region_t strict_region_plan(uint64_t slice, uint64_t key_slots) {
+  strict_region_t r;
+  r.list = 4 * kTriagePlaneCount * slice;
+  r.keyslot = r.list + 4 * slice;
+  r.block = r.keyslot + 4 * slice;
+  r.slots = r.block + kTriageBlockBytes;
+  r.kflags = r.slots + 4 * key_slots;
+  r.ktabs = r.kflags + 4 * key_slots + 256;
+  r.bytes = r.ktabs + kKeyTabBytes * key_slots;
+  return r;
+}
+size_t strict_triage_bytes(uint64_t slice, uint64_t key_slots);
 struct strict_ws_t {
   void* base = nullptr;       // strict_workspace_bytes()
-  void* triage = nullptr;     // strict_triage_bytes(triage_cap), or null (keyed launches)
+  void* triage = nullptr;     // strict_triage_bytes(triage_cap, key_slots_cap), or null (keyed)
   uint64_t triage_cap = 0;    // items
+  uint64_t key_slots_cap = 0; // slots
   uint64_t slice = 0;         // strict_triage_slice(n) of the launch this was handed out for
+  uint64_t key_slots = 0;     // strict_keys_slots(slice) of that launch
 };
+// For the last unkeyed two-pass launch queued on the current device: distinct keys tabulated,
+// items that read a shared table, items on their own path. Synchronises `stream`.
+hipError_t strict_keyset_stats(uint64_t out[3], hipStream_t stream);
 // keys (optional): pre-decompressed key tables with vote_key = per-item key index.
 // Builds the current device's lazily built strict tables (nw_prepare).
 hipError_t prepare_strict_tables();

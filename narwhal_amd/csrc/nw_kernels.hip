@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <atomic>
 #include <mutex>
+#include <vector>
 
 namespace nw {
 
@@ -122,6 +123,7 @@ __device__ __forceinline__ const T* opaque_ptr(const T* p) {
 struct strict_src_global {
   static constexpr bool kPre = false;
   static constexpr bool kScalars = false;
+  static constexpr bool kSharedA = false;
   const uint32_t* pk;    // 8 words
   const uint32_t* sig;   // 16 words: R || s
   const uint32_t* msg;   // 8 words
@@ -160,13 +162,24 @@ struct strict_src_global {
 // point pt (0 = A, 1 = R) of survivor q at xs[(10 pt + k) cap + q]. y is the encoding's own
 // (fe_frombytes), Z = 1, T = x y: exactly the point ge_frombytes returned. The same pass also
 // ran the scalar phase (nw_strict.hpp strict_triage_scalars) and stored the ladder's digit
-// word t at plane 20 + t and vneg | W << 1 at plane 41.
+// word t at plane 20 + t and vneg | W << 1 at plane 41. A survivor whose key has a slot in the
+// slice's key set (nw_strict.hpp keyset_probe) has kMetaSharedA set in plane 41 and the slot
+// number in plane 0 (A's x limb 0; its limbs 1..9 are not written): its table j * A is
+// ktabs[8 slot ..], built once by k_strict_keys_build.
 constexpr uint64_t kTriagePlanes = 20 + kStrictDigitWords + 1;
 struct strict_src_pre : strict_src_global {
   static constexpr bool kPre = true;
   static constexpr bool kScalars = true;
+  static constexpr bool kSharedA = true;
   const uint32_t* xs;
   uint64_t cap, q;
+  const ge_cached_pk* ktabs;
+  __device__ uint32_t shared_slot() const {
+    const uint32_t* x = opaque_ptr(xs);
+    const uint32_t meta = x[(uint64_t)(20 + kStrictDigitWords) * cap + q];
+    return (meta & kMetaSharedA) ? x[q] : kNoSlot;
+  }
+  __device__ const void* shared_tabs() const { return ktabs; }
   __device__ bool point(int pt, ge& P) const {
     uint32_t w[8];
     if (pt) R(w); else A(w);
@@ -181,7 +194,9 @@ struct strict_src_pre : strict_src_global {
   __device__ uint32_t digit_word(int t) const {
     return opaque_ptr(xs)[(uint64_t)(20 + t) * cap + q];
   }
-  __device__ uint32_t scalar_meta() const { return digit_word(kStrictDigitWords); }
+  __device__ uint32_t scalar_meta() const {
+    return digit_word(kStrictDigitWords) & ~kMetaSharedA;
+  }
 };
 
 // Limb planes of the pending votes of a slice: X' limb k at planes[k S + i], Z' limb k at
@@ -356,13 +371,19 @@ __global__ __launch_bounds__(256, NW_TRIAGE_WAVES) void k_strict_triage(
     const uint32_t* __restrict__ msgs, uint32_t msg_stride_words, const uint32_t* __restrict__ pks,
     const uint32_t* __restrict__ sigs, uint64_t i0, uint64_t ns, int32_t* __restrict__ status,
     uint32_t* __restrict__ xs, uint64_t cap, uint32_t* __restrict__ list,
-    uint32_t* __restrict__ count) {
+    uint32_t* __restrict__ count, const uint32_t* __restrict__ keyslot,
+    const uint32_t* __restrict__ kflags) {
   const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const bool active = j < ns;
   const uint64_t i = i0 + (active ? j : 0);
   const strict_src_global src{pks + 8 * i, sigs + 16 * i, msgs + (uint64_t)msg_stride_words * i};
+  // the key's slot in the slice's set (keyslot == nullptr: the set is off); an idle lane of the
+  // last wave takes item i0's
+  const uint32_t slot = keyslot ? keyslot[active ? j : 0] : kNoSlot;
+  const uint32_t keyflags = slot != kNoSlot ? kflags[slot] : kNoSlot;
   fe xa, xr;
-  const int st = strict_triage(src, g_consts.sk, xa, xr);
+  const int st = strict_triage(src, g_consts.sk, xa, xr, keyflags,
+                               [](bool b) { return __ballot(b) != 0; });
   if (active && st != NW_OK) status[i] = st;
   const bool keep = active && st == NW_OK;
   const uint64_t m = __ballot(keep);
@@ -376,18 +397,68 @@ __global__ __launch_bounds__(256, NW_TRIAGE_WAVES) void k_strict_triage(
   if (!keep) return;
   const uint64_t pos = (uint64_t)base + rank;
   list[pos] = (uint32_t)j;
+  if (slot != kNoSlot) {
+    xs[pos] = slot;
+  } else {
 #pragma unroll
-  for (int k = 0; k < 10; ++k) {
-    xs[(uint64_t)k * cap + pos] = xa.v[k];
-    xs[(uint64_t)(10 + k) * cap + pos] = xr.v[k];
+    for (int k = 0; k < 10; ++k) xs[(uint64_t)k * cap + pos] = xa.v[k];
   }
+#pragma unroll
+  for (int k = 0; k < 10; ++k) xs[(uint64_t)(10 + k) * cap + pos] = xr.v[k];
   // the survivors' scalar phase, after the x limbs are stored (nothing of the decompression
   // is live here); the lanes of rejected items have left
   uint32_t dig[kStrictDigitWords], meta;
   strict_triage_scalars<NW_BWIN>(src, dig, meta);
 #pragma unroll
   for (int t = 0; t < kStrictDigitWords; ++t) xs[(uint64_t)(20 + t) * cap + pos] = dig[t];
-  xs[(uint64_t)(20 + kStrictDigitWords) * cap + pos] = meta;
+  xs[(uint64_t)(20 + kStrictDigitWords) * cap + pos] = meta | (slot != kNoSlot ? kMetaSharedA : 0u);
+}
+
+// ---- the slice's key set (nw_strict.hpp keyset_probe / keyset_build) ----
+struct keyset_atomics {
+  __device__ uint32_t load(const uint32_t* p) const {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __device__ uint32_t cas(uint32_t* p, uint32_t expect, uint32_t val) const {
+    return atomicCAS(p, expect, val);
+  }
+  __device__ void inc(uint32_t* p) const { atomicAdd(p, 1u); }
+};
+// One lane per item of the slice: keyslot[j] = the slot of item j's key, or kNoSlot.
+// with[block & (kKeyStatLanes - 1)] += the block's items with a slot (diagnostics: one atomic
+// per block, spread over kKeyStatLanes addresses).
+__global__ __launch_bounds__(256) void k_strict_keys_probe(
+    const uint32_t* __restrict__ pks, uint64_t i0, uint64_t ns, uint32_t* slots, uint32_t cap,
+    uint32_t limit, uint32_t* nkeys, uint32_t* __restrict__ keyslot,
+    unsigned long long* __restrict__ with_ctr) {
+  __shared__ uint32_t s_with[4];
+  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool active = j < ns;
+  uint32_t slot = kNoSlot;
+  if (active) {
+    slot = keyset_probe(slots, cap, limit, nkeys, pks, i0, (uint32_t)j, keyset_atomics{});
+    keyslot[j] = slot;
+  }
+  const uint64_t m = __ballot(slot != kNoSlot);
+  if ((threadIdx.x & 63u) == 0) s_with[threadIdx.x >> 6] = (uint32_t)__builtin_popcountll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint32_t with = s_with[0] + s_with[1] + s_with[2] + s_with[3];
+    if (with) atomicAdd(with_ctr + (blockIdx.x & (kKeyStatLanes - 1)), (unsigned long long)with);
+  }
+}
+// One lane per slot: an owned slot's flags and table. stats[0] += owned slots.
+__global__ __launch_bounds__(256) void k_strict_keys_build(
+    const uint32_t* __restrict__ pks, uint64_t i0, const uint32_t* __restrict__ slots,
+    uint32_t cap, uint32_t* __restrict__ kflags, ge_cached_pk* __restrict__ ktabs,
+    unsigned long long* __restrict__ stats) {
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool owned = s < cap && slots[s] != 0;
+  const uint64_t m = __ballot(owned);
+  if (m == 0) return;
+  if ((threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(m))
+    atomicAdd(stats, (unsigned long long)__builtin_popcountll(m));
+  if (owned) keyset_build(slots, s, pks, i0, g_consts.sk, kflags, ktabs);
 }
 
 // The list's items (persistent, as k_verify_strict): strict_verify_core on the points
@@ -397,7 +468,7 @@ __global__ __launch_bounds__(256, NW_STRICT_WAVES) void k_verify_strict_pre(
     const uint32_t* __restrict__ sigs, uint64_t i0, const uint32_t* __restrict__ list,
     const uint32_t* __restrict__ count, const uint32_t* __restrict__ xs, uint64_t cap,
     int32_t* __restrict__ status, ge_cached_pk* __restrict__ tabs,
-    const ge_niels_pad* __restrict__ btw) {
+    const ge_niels_pad* __restrict__ btw, const ge_cached_pk* __restrict__ ktabs) {
   const uint64_t n = *count;
 #if NW_BWIN == 8
   __shared__ ge_niels s_btab[129];
@@ -420,7 +491,7 @@ __global__ __launch_bounds__(256, NW_STRICT_WAVES) void k_verify_strict_pre(
     const uint64_t q = active ? q0 : n - 1;
     const uint64_t i = i0 + list[q];
     const strict_src_pre src{{pks + 8 * i, sigs + 16 * i, msgs + (uint64_t)msg_stride_words * i},
-                             xs, cap, q};
+                             xs, cap, q, ktabs};
 #if NW_STRICT_PF && NW_BWIN != 8
     const int st = strict_verify_core<NW_BWIN>(src, g_consts.sk, bt, tabA, tabR, WaveMax{},
                                                pf_lds{(uint32_t)__builtin_amdgcn_readfirstlane(
@@ -1012,8 +1083,9 @@ bool strict_triage_on() {   // NW_STRICT_TRIAGE=0: one pass (k_verify_strict), A
 static size_t strict_keyed_region_bytes() { return 4 * kKeyedSliceMax + 256; }
 size_t strict_workspace_bytes() { return strict_tabs_bytes() + strict_keyed_region_bytes(); }
 // The two-pass path's slice (k_strict_triage / k_verify_strict_pre): kTriagePlanes words and
-// a list entry per item, then the count; a region of its own, sized for the launch
-// (172 B per item: 2.9 GB at the limit, 2.15 GB for config 4's 12.5M items). The limit is
+// a list entry and a key slot per item, then the count and the key set (nw_kernels.h
+// strict_region_plan); a region of its own, sized for the launch (176 B per item and 1 KB
+// per key slot: 3.0 GB at the limit, 2.3 GB for config 4's 12.5M items). The limit is
 // large: config 4 is one slice, so the second pass's last, partly filled round over the
 // resident lanes comes once per launch.
 constexpr uint64_t kTriageSlice = 1ull << 24;
@@ -1027,7 +1099,57 @@ uint64_t strict_triage_slice(uint64_t n) {
   lim = (lim + 63) & ~63ull;
   return std::min<uint64_t>(lim, (std::max<uint64_t>(n, 1) + 63) & ~63ull);
 }
-size_t strict_triage_bytes(uint64_t slice) { return 4 * (kTriagePlanes + 1) * slice + 256; }
+// The slice's key set (nw_strict.hpp keyset_probe): slots of the open-addressing table, a power
+// of two; at most half of them are filled. NW_STRICT_KEYS = slots (clamped to [64, 2^20] and
+// rounded up to a power of two; 0 = no key set, the launch sequence without it), read per
+// launch; default 2^16 (64 MB of tables), fewer for a small slice (strict_keys_plan).
+uint64_t strict_keys_slots(uint64_t slice) {
+  uint64_t req = kKeySlotsDefault;
+  if (const char* e = getenv("NW_STRICT_KEYS")) req = strtoull(e, nullptr, 10);
+  return strict_keys_plan(req, slice);
+}
+static_assert(kTriagePlanes == kTriagePlaneCount && sizeof(ge_cached_pk) * 8 == kKeyTabBytes,
+              "strict_region_plan's layout");
+size_t strict_triage_bytes(uint64_t slice, uint64_t key_slots) {
+  return strict_region_plan(slice, key_slots).bytes;
+}
+
+// Diagnostics of the last unkeyed two-pass launch per device (strict_keyset_stats).
+namespace {
+struct keyset_record_t {
+  const char* dev = nullptr;   // the region's block (strict_region_plan)
+  uint64_t n = 0;
+  bool valid = false, on = false;
+};
+std::mutex g_keyset_m;
+keyset_record_t g_keyset_last[64];
+}  // namespace
+hipError_t strict_keyset_stats(uint64_t out[3], hipStream_t stream) {
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  keyset_record_t rec;
+  {
+    std::lock_guard<std::mutex> g(g_keyset_m);
+    if (dev >= 0 && dev < 64) rec = g_keyset_last[dev];
+  }
+  out[0] = out[1] = out[2] = 0;
+  if (!rec.valid) return hipSuccess;
+  e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) return e;
+  if (!rec.on) {
+    out[2] = rec.n;
+    return hipSuccess;
+  }
+  static_assert(1024 + 8 * kKeyStatLanes <= kTriageBlockBytes, "the block's counters");
+  std::vector<unsigned long long> h(kTriageBlockBytes / 8);
+  e = hipMemcpy(h.data(), rec.dev, kTriageBlockBytes, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return e;
+  out[0] = h[1];
+  for (uint32_t t = 0; t < kKeyStatLanes; ++t) out[1] += h[128 + t];
+  out[2] = rec.n - out[1];
+  return hipSuccess;
+}
 
 hipError_t launch_verify_strict(const uint32_t* msgs, uint32_t msg_stride_words,
                                 const uint32_t* pks, const uint32_t* sigs, uint64_t n,
@@ -1047,22 +1169,56 @@ hipError_t launch_verify_strict(const uint32_t* msgs, uint32_t msg_stride_words,
     // the slice Lease::strict_ws chose for this launch (one read of NW_TRIAGE_SLICE per launch)
     const uint64_t slice = wsp.slice;
     if (!wsp.triage || slice == 0 || wsp.triage_cap < slice) return hipErrorInvalidValue;
+    if (wsp.key_slots > wsp.key_slots_cap) return hipErrorInvalidValue;
+    const uint32_t kcap = (uint32_t)wsp.key_slots;   // 0: no key set
+    const strict_region_t rg = strict_region_plan(slice, kcap);
+    if (rg.bytes > strict_triage_bytes(wsp.triage_cap, wsp.key_slots_cap)) return hipErrorInvalidValue;
+    char* const region = static_cast<char*>(wsp.triage);
     uint32_t* const xs = static_cast<uint32_t*>(wsp.triage);
-    uint32_t* const list = xs + kTriagePlanes * slice;
-    uint32_t* const count = list + slice;
+    uint32_t* const list = reinterpret_cast<uint32_t*>(region + rg.list);
+    uint32_t* const keyslot = kcap ? reinterpret_cast<uint32_t*>(region + rg.keyslot) : nullptr;
+    uint32_t* const count = reinterpret_cast<uint32_t*>(region + rg.block);
+    uint32_t* const nkeys = count + 1;
+    unsigned long long* const stats = reinterpret_cast<unsigned long long*>(region + rg.block + 8);
+    unsigned long long* const with_ctr =
+        reinterpret_cast<unsigned long long*>(region + rg.block + 1024);
+    uint32_t* const kslots = reinterpret_cast<uint32_t*>(region + rg.slots);
+    uint32_t* const kflags = reinterpret_cast<uint32_t*>(region + rg.kflags);
+    ge_cached_pk* const ktabs = reinterpret_cast<ge_cached_pk*>(region + rg.ktabs);
+    if (kcap) {
+      hipError_t e = hipMemsetAsync(stats, 0, kTriageBlockBytes - 8, stream);
+      if (e != hipSuccess) return e;
+    }
+    {
+      int dev = 0;
+      if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
+        std::lock_guard<std::mutex> g(g_keyset_m);
+        g_keyset_last[dev] = keyset_record_t{region + rg.block, n, true, kcap != 0};
+      }
+    }
     // equal slices of at most `slice` items
     const uint64_t nsl = (n + slice - 1) / slice;
     const uint64_t per = (n + nsl - 1) / nsl;
     for (uint64_t i0 = 0; i0 < n; i0 += per) {
       const uint64_t ns = std::min(per, n - i0);
-      hipError_t e = hipMemsetAsync(count, 0, 4, stream);
+      hipError_t e = hipMemsetAsync(count, 0, 8, stream);   // count and nkeys
       if (e != hipSuccess) return e;
+      if (kcap) {
+        // the slice's key set: each key's slot, then each slot's flags and table, once
+        e = hipMemsetAsync(kslots, 0, 4 * (size_t)kcap, stream);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_strict_keys_probe, dim3(grid_for(ns, 256)), dim3(256), 0, stream,
+                           pks, i0, ns, kslots, kcap, kcap / 2, nkeys, keyslot, with_ctr);
+        hipLaunchKernelGGL(k_strict_keys_build, dim3(grid_for(kcap, 256)), dim3(256), 0, stream,
+                           pks, i0, kslots, kcap, kflags, ktabs, stats);
+      }
       hipLaunchKernelGGL(k_strict_triage, dim3(grid_for(ns, 256)), dim3(256), 0, stream, msgs,
-                         msg_stride_words, pks, sigs, i0, ns, status, xs, slice, list, count);
+                         msg_stride_words, pks, sigs, i0, ns, status, xs, slice, list, count,
+                         keyslot, kflags);
       hipLaunchKernelGGL(k_verify_strict_pre,
                          dim3(std::min<uint64_t>(strict_grid(), grid_for(ns, 256))), dim3(256),
                          0, stream, msgs, msg_stride_words, pks, sigs, i0, list, count, xs,
-                         slice, status, static_cast<ge_cached_pk*>(workspace), btw);
+                         slice, status, static_cast<ge_cached_pk*>(workspace), btw, ktabs);
     }
     if (bitmap)
       hipLaunchKernelGGL(k_status_bitmap, dim3(grid_for(n, 256)), dim3(256), 0, stream, status,

@@ -205,6 +205,97 @@ NW_HD void build_table8(Tab* tab, const ge& P, const fe& d2) {
   }
 }
 
+// ---- the call's key set (two-pass path, DESIGN.md 5 "Round 8") ----
+// The items of a call share a handful of public keys, and ge_frombytes(A), small_order_by_y(A)
+// and build_table8(tabA) are pure functions of the 32 key bytes: a slice of items runs them
+// once per distinct key. The set is an open-addressing table of `cap` (a power of two) slots,
+// slots[s] = owner item index + 1 (the slice's first item whose key claimed the slot) or 0.
+// A key's first slot is keyset_hash(words) & (cap - 1):
+//     h = 0x9e3779b9
+//     for t = 0..7:  h = (h ^ w[t]) * 0x85ebca6b;  h ^= h >> 15        (all mod 2^32)
+//     h = h * 0xc2b2ae35;  h ^= h >> 16
+// (every bit of the key reaches the low bits: keys that differ in one high bit of a word do not
+// start at the same slot), followed by the next kKeyProbes - 1 slots (mod cap). Two encodings of one point (y and
+// y + p) are two keys: the comparison is over the 32 bytes.
+constexpr uint32_t kNoSlot = 0xffffffffu;
+constexpr int kKeyProbes = 8;
+// probes of an item that arrives once the set holds `limit` keys (it only looks its key up):
+// the slice then has more keys than the set takes, most lookups miss, and a miss costs every
+// probe it makes; a key that sits further down its chain is then not found by such an item,
+// which runs its own path
+constexpr int kKeyLookupProbes = 2;
+// meta plane bit of a survivor whose A comes from the key set (plane 0 then holds its slot)
+constexpr uint32_t kMetaSharedA = 1u << 31;
+
+NW_HD uint32_t keyset_hash(const uint32_t w[8]) {
+  uint32_t h = 0x9e3779b9u;
+#pragma unroll
+  for (int t = 0; t < 8; ++t) {
+    h = (h ^ w[t]) * 0x85ebca6bu;
+    h ^= h >> 15;
+  }
+  h *= 0xc2b2ae35u;
+  return h ^ (h >> 16);
+}
+
+// The slot of item j's key (pks[8 (i0 + j)..]) in the slice's set, or kNoSlot. While fewer
+// than `limit` keys are in the set an empty slot on the probe chain is claimed (a 32-bit
+// compare-and-swap 0 -> j + 1, then *nkeys += 1; concurrent claims may overshoot limit, never
+// cap); afterwards the chain is looked up only. An occupied slot, found so or after a lost
+// swap, is this item's iff its owner's 32 key bytes equal this item's: the keys are the
+// call's input, immutable, so a slot has no busy state and nothing here waits. At most
+// kKeyProbes iterations (kKeyLookupProbes when it only looks up), whatever the other lanes do.
+// at: load(p) (a fresh value of a word other lanes swap), cas(p, expect, val) -> old value,
+// inc(p). The device's are atomics; the host self-check's plain loads and stores.
+template <class Atomics>
+NW_HD uint32_t keyset_probe(uint32_t* slots, uint32_t cap, uint32_t limit, uint32_t* nkeys,
+                            const uint32_t* pks, uint64_t i0, uint32_t j, const Atomics& at) {
+  uint32_t w[8];
+  const uint32_t* mine = pks + 8 * (i0 + j);
+#pragma unroll
+  for (int t = 0; t < 8; ++t) w[t] = mine[t];
+  const bool insert = at.load(nkeys) < limit;
+  uint32_t s = keyset_hash(w) & (cap - 1);
+  const int probes = insert ? kKeyProbes : kKeyLookupProbes;
+#pragma unroll 1
+  for (int p = 0; p < probes; ++p, s = (s + 1) & (cap - 1)) {
+    uint32_t owner = at.load(slots + s);
+    if (owner == 0) {
+      if (!insert) return kNoSlot;   // not in the set (or not yet): this item's own path
+      owner = at.cas(slots + s, 0u, j + 1);
+      if (owner == 0) {
+        at.inc(nkeys);
+        return s;
+      }
+    }
+    const uint32_t* theirs = pks + 8 * (i0 + (owner - 1));
+    uint32_t d = 0;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) d |= w[t] ^ theirs[t];
+    if (d == 0) return s;
+  }
+  return kNoSlot;
+}
+
+// One slot of the set: the owner's key decompressed and tested once, its flags (kKeyDecoded,
+// kKeySmall) and, when it decodes, its table j * A in the form the ladder reads. The same
+// functions the per-item path calls, so the same limbs.
+template <class Tab>
+NW_HD void keyset_build(const uint32_t* slots, uint32_t s, const uint32_t* pks, uint64_t i0,
+                        const strict_consts& K, uint32_t* kflags, Tab* ktabs) {
+  const uint32_t owner = slots[s];
+  if (owner == 0) return;
+  uint32_t w[8];
+  const uint32_t* key = pks + 8 * (i0 + (owner - 1));
+#pragma unroll
+  for (int t = 0; t < 8; ++t) w[t] = key[t];
+  ge P;
+  const bool ok = ge_frombytes(P, w, K.k);
+  const bool small = small_order_by_y(P.Y, K.small_y);
+  kflags[s] = (ok ? kKeyDecoded : 0u) | (small ? kKeySmall : 0u);
+  if (ok) build_table8(ktabs + 8 * (uint64_t)s, P, K.k.d2);
+}
+
 // Inputs of one strict verification, fetched when needed (so nothing but the decompression
 // is live across the decompression): A(w) / R(w) / S(w) give the 8 LE words of the public
 // key, of R and of s; k(x) gives k = H(R || A || M) mod l. The kernel's source reloads
@@ -212,6 +303,7 @@ NW_HD void build_table8(Tab* tab, const ge& P, const fe& d2) {
 struct strict_src_arrays {
   static constexpr bool kPre = false;   // A and R decompressed here (see strict_verify_core)
   static constexpr bool kScalars = false;   // the scalar phase runs here (strict_scalar_phase)
+  static constexpr bool kSharedA = false;   // every item tabulates its own A
   const uint32_t* a;
   const uint32_t* r;
   const uint32_t* s;
@@ -713,8 +805,13 @@ NW_HD void strict_triage_scalars(const Src& src, uint32_t dig[kStrictDigitWords]
 // order, in strict_verify_core's order. Returns the status of an item that fails one of
 // them, NW_OK otherwise; xa / xr get the x of A and R (the rest of each point is its
 // encoding's y, Z = 1 and T = x y: exactly what ge_frombytes returned).
-template <class Src>
-NW_HD int strict_triage(const Src& src, const strict_consts& K, fe& xa, fe& xr) {
+// keyflags: kNoSlot for an item that decompresses its own key; otherwise the flag word of its
+// key's slot in the call's key set (keyset_build: kKeyDecoded, kKeySmall), which stands for
+// the A iteration's results (xa is then not written). wave_any(b): b of any lane of the wave
+// (identity on the host): the A iteration runs only while some lane has no slot.
+template <class Src, class WaveAny>
+NW_HD int strict_triage(const Src& src, const strict_consts& K, fe& xa, fe& xr,
+                        uint32_t keyflags, WaveAny wave_any) {
   uint32_t Sw[8];
   src.S(Sw);
   const bool s_high = (Sw[7] >> 29) != 0;
@@ -722,20 +819,30 @@ NW_HD int strict_triage(const Src& src, const strict_consts& K, fe& xa, fe& xr) 
 #pragma unroll
   for (int t = 0; t < 8; ++t) s.w[t] = Sw[t];
   const bool s_canon = sc_is_canonical(s);
-  bool okA = false, okR = false, smallA = false, smallR = false;
+  const bool own = keyflags == kNoSlot;
+  bool okA = (keyflags & kKeyDecoded) != 0, smallA = (keyflags & kKeySmall) != 0;
+  bool okR = false, smallR = false;
   // A, then R, in one rolled loop (one copy of the square-root chain: registers, code size)
 #pragma unroll 1
-  for (int pt = 0; pt < 2; ++pt) {
+  for (int pt = wave_any(own) ? 0 : 1; pt < 2; ++pt) {
     uint32_t w[8];
     if (pt) src.R(w); else src.A(w);
     ge P;
     const bool ok = ge_frombytes(P, w, K.k);
     const bool small = small_order_by_y(P.Y, K.small_y);
-    if (pt == 0) { okA = ok; smallA = small; xa = P.X; } else { okR = ok; smallR = small; xr = P.X; }
+    if (pt == 0) {
+      if (own) { okA = ok; smallA = small; xa = P.X; }
+    } else {
+      okR = ok; smallR = small; xr = P.X;
+    }
   }
   return s_high ? NW_ERR_S_HIGH_BITS : !okA ? NW_ERR_A_DECODE
        : !s_canon ? NW_ERR_S_NONCANONICAL : !okR ? NW_ERR_R_DECODE
        : smallR ? NW_ERR_R_SMALL_ORDER : smallA ? NW_ERR_A_SMALL_ORDER : NW_OK;
+}
+template <class Src>
+NW_HD int strict_triage(const Src& src, const strict_consts& K, fe& xa, fe& xr) {
+  return strict_triage(src, K, xa, xr, kNoSlot, [](bool b) { return b; });
 }
 
 template <int BW, class BTab, class Src, class WaveMax, class PF = pf_none, class Tab = ge_cached>
@@ -747,8 +854,15 @@ NW_HD int strict_verify_core(const Src& src, const strict_consts& K, const BTab&
   // code object): P, its small-order flag and its 8-entry table j * P. Only the point is
   // live here: the scalars are computed afterwards (register pressure).
   bool okA = false, smallA = false, okR = false, smallR = false;
+  // kSharedA (the two-pass path with the call's key set): a lane whose key has a slot reads
+  // the slot's table j * A, which keyset_build made once for the slice, in place of its
+  // per-lane one; the A iteration runs only while some lane of the wave has no slot (such a
+  // wave's other lanes run it on stale limbs into their per-lane table, which they then
+  // do not read).
+  int pt0 = 0;
+  if constexpr (Src::kSharedA) pt0 = wave_max(src.shared_slot() == kNoSlot ? 1 : 0) ? 0 : 1;
 #pragma unroll 1
-  for (int pt = 0; pt < 2; ++pt) {
+  for (int pt = pt0; pt < 2; ++pt) {
     ge P;
     bool ok;
     if constexpr (Src::kPre) {
@@ -807,6 +921,18 @@ NW_HD int strict_verify_core(const Src& src, const strict_consts& K, const BTab&
     }
   }
   W = wave_max(W);
+  // this round's A table: the lane's own, or its key's slot of the set (slot < cap by
+  // keyset_probe, 8 entries per slot)
+  uint32_t aslot = kNoSlot;
+  if constexpr (Src::kSharedA) aslot = src.shared_slot();
+  auto tabA_entry = [&](int e) -> const Tab* {
+    if constexpr (Src::kSharedA) {
+      const Tab* sh = static_cast<const Tab*>(src.shared_tabs()) + 8 * (uint64_t)aslot;
+      return (aslot == kNoSlot ? static_cast<const Tab*>(tabA) : sh) + e;
+    } else {
+      return tabA + e;
+    }
+  };
   if (NW_STRICT_STOP == 4) return W + (vneg ? 16 : 0) + (okR ? 64 : 0);
   const uint32_t* const ud = dig;
   const uint32_t* const vd = dig + 8;
@@ -849,7 +975,9 @@ NW_HD int strict_verify_core(const Src& src, const strict_consts& K, const BTab&
         return d ? static_cast<const void*>(bt.entry(t1 ? 1 : 0, d < 0 ? -d : d)) : nullptr;
       }
       const int ad = d < 0 ? -d : d;
-      return d ? static_cast<const void*>((slot == 0 ? tabA : tabR) + (ad - 1)) : nullptr;
+      return d ? static_cast<const void*>(slot == 0 ? tabA_entry(ad - 1)
+                                                    : static_cast<const Tab*>(tabR) + (ad - 1))
+               : nullptr;
     };
     auto nslots_of = [&](int j) {
       const int p0 = 4 * j, p1 = 4 * j + 128;
@@ -942,7 +1070,8 @@ NW_HD int strict_verify_core(const Src& src, const strict_consts& K, const BTab&
         const int ad = d < 0 ? -d : d;
         ge_cached e;
         if (slot < 2) {
-          tab_get(slot == 0 ? tabA : tabR, ad - 1, e);
+          if (slot == 0) tab_get(tabA_entry(ad - 1), 0, e);
+          else tab_get(tabR, ad - 1, e);
         } else {
           bt((slot == 3 || !has0) ? 1 : 0, ad, e);
         }

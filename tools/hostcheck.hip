@@ -372,6 +372,107 @@ int hc_keyed_vote_check(const uint8_t pk[32], const uint8_t sig[64], const uint8
   return fe_isnegative(x) == (st & 1) ? 0 : 1;
 }
 
+// Config 4's two passes with the call's key set, as launch_verify_strict runs a slice:
+// keyset_probe for every item (the "atomics" are plain loads and stores: one thread), then
+// keyset_build for every slot, then per item strict_triage on the slot's flags,
+// strict_triage_scalars, and the ladder with the slot's table for tabA (the prefetch branch;
+// a slotted item's per-lane table is left as garbage). The key set lies in one allocation at
+// the offsets of strict_region_plan, sized as Lease::strict_ws sizes it. key_slots: as
+// NW_STRICT_KEYS (0 = off); bw = -16 or -24. keyslot_out (n words, optional): each item's
+// slot or kNoSlot; stats: keys tabulated, items with a slot, items without.
+struct plain_atomics {
+  uint32_t load(const uint32_t* p) const { return *p; }
+  uint32_t cas(uint32_t* p, uint32_t expect, uint32_t val) const {
+    const uint32_t old = *p;
+    if (old == expect) *p = val;
+    return old;
+  }
+  void inc(uint32_t* p) const { ++*p; }
+};
+struct src_arrays_keys : src_arrays_pre_scalars {
+  static constexpr bool kSharedA = true;
+  const ge_cached_pk* ktabs;
+  uint32_t shared_slot() const {
+    return (words[kStrictDigitWords] & kMetaSharedA) ? xa.v[0] : kNoSlot;
+  }
+  const void* shared_tabs() const { return ktabs; }
+  uint32_t scalar_meta() const { return words[kStrictDigitWords] & ~kMetaSharedA; }
+};
+extern "C++" {
+template <int BW, class BTab>
+static int keyset_item(src_arrays_keys& src, const BTab& bt, uint32_t slot, const uint32_t* kflags) {
+  const uint32_t keyflags = slot != kNoSlot ? kflags[slot] : kNoSlot;
+  for (int t = 0; t < 10; ++t) src.xa.v[t] = 0xdeadbeefu;
+  const int st = strict_triage(static_cast<const strict_src_arrays&>(src), SK, src.xa, src.xr,
+                               keyflags, [](bool b) { return b; });
+  if (st != NW_OK) return st;
+  if (slot != kNoSlot) src.xa.v[0] = slot;
+  strict_triage_scalars<BW>(static_cast<const strict_src_arrays&>(src), src.words,
+                            src.words[kStrictDigitWords]);
+  if (slot != kNoSlot) src.words[kStrictDigitWords] |= kMetaSharedA;
+  ge_cached_pk pa[8], pr[8];
+  memset(pa, 0xa5, sizeof(pa));
+  pf_host_state ps;
+  return strict_verify_core<BW>(src, SK, bt, pa, pr, [](int w) { return w; }, pf_host{&ps});
+}
+}
+int hc_verify_strict_keyset_many(const uint8_t* pks, const uint8_t* sigs, const uint8_t* k32,
+                                 uint32_t n, uint64_t key_slots, int bw, int32_t* status_out,
+                                 uint32_t* keyslot_out, uint64_t stats[3]) {
+  init();
+  if (n == 0) return 0;
+  const uint64_t slice = ((uint64_t)n + 63) & ~63ull;
+  const uint32_t cap = (uint32_t)strict_keys_plan(key_slots, slice);
+  const strict_region_t rg = strict_region_plan(slice, cap);
+  // only the parts this check uses are touched; the planes before them stay unallocated
+  const uint64_t first = rg.keyslot;
+  uint8_t* mem = static_cast<uint8_t*>(malloc(rg.bytes - first));
+  if (!mem) return -1;
+  uint32_t* keyslot = reinterpret_cast<uint32_t*>(mem + (rg.keyslot - first));
+  uint32_t* nkeys = reinterpret_cast<uint32_t*>(mem + (rg.block - first)) + 1;
+  uint32_t* slots = reinterpret_cast<uint32_t*>(mem + (rg.slots - first));
+  uint32_t* kflags = reinterpret_cast<uint32_t*>(mem + (rg.kflags - first));
+  ge_cached_pk* ktabs = reinterpret_cast<ge_cached_pk*>(mem + (rg.ktabs - first));
+  // the keys as aligned words (the device's pks array)
+  uint32_t* pkw = static_cast<uint32_t*>(malloc(32 * (size_t)n));
+  if (!pkw) { free(mem); return -1; }
+  memcpy(pkw, pks, 32 * (size_t)n);
+  *nkeys = 0;
+  memset(slots, 0, 4 * (size_t)cap);
+  uint64_t with = 0, owned = 0;
+  for (uint32_t j = 0; j < n; ++j) {
+    keyslot[j] = cap ? keyset_probe(slots, cap, cap / 2, nkeys, pkw, 0, j, plain_atomics{})
+                     : kNoSlot;
+    with += keyslot[j] != kNoSlot;
+  }
+  for (uint32_t s = 0; s < cap; ++s) {
+    owned += slots[s] != 0;
+    keyset_build(slots, s, pkw, 0, SK, kflags, ktabs);
+  }
+  for (uint32_t j = 0; j < n; ++j) {
+    uint32_t Aw[8], Rw[8], Sw[8], kw[8];
+    load8(Aw, pks + 32 * (size_t)j); load8(Rw, sigs + 64 * (size_t)j);
+    load8(Sw, sigs + 64 * (size_t)j + 32); load8(kw, k32 + 32 * (size_t)j);
+    src_arrays_keys src{};
+    src.a = Aw; src.r = Rw; src.s = Sw; src.k = kw;
+    src.ktabs = ktabs;
+    status_out[j] = bw == -24
+        ? keyset_item<24>(src, btab_lazy_entry{{BT, &SK.k.d2}, {}}, keyslot[j], kflags)
+        : keyset_item<16>(src, btab_wide{BTW, BTW_N}, keyslot[j], kflags);
+    if (keyslot_out) keyslot_out[j] = keyslot[j];
+  }
+  if (stats) { stats[0] = owned; stats[1] = with; stats[2] = n - with; }
+  free(pkw);
+  free(mem);
+  return 0;
+}
+// The documented hash of a key (nw_strict.hpp keyset_hash), for the tests' numpy restatement.
+uint32_t hc_keyset_hash(const uint8_t pk[32]) {
+  uint32_t w[8];
+  load8(w, pk);
+  return keyset_hash(w);
+}
+
 // Entry j of the wide B table half h (ypx || ymx || xy2d as 30 limbs), for the table test.
 void hc_wide_btab_entry(int h, uint32_t j, uint32_t out[30]) {
   init();
@@ -379,3 +480,65 @@ void hc_wide_btab_entry(int h, uint32_t j, uint32_t out[30]) {
 }
 
 }
+
+#ifdef KEYSET_SAN_MAIN
+// make keysetsan && tools/keyset_san: the key set's sizing and region planning
+// (nw_kernels.h strict_keys_plan / strict_region_plan) and the probe -> build -> triage ->
+// ladder sequence over that region, as a stand-alone program under AddressSanitizer / UBSan.
+#include <stdio.h>
+#include <vector>
+static int san_fail(const char* what, uint64_t a, uint64_t b) {
+  fprintf(stderr, "keyset_san: %s (%llu, %llu)\n", what, (unsigned long long)a, (unsigned long long)b);
+  return 1;
+}
+int main() {
+  const uint64_t reqs[] = {0, 1, 63, 64, 65, 1000, 65536, 1ull << 20, (1ull << 20) + 1, 1ull << 40, ~0ull};
+  const uint64_t slices[] = {0, 64, 128, 1536, 196608, 1ull << 24};
+  for (uint64_t rq : reqs)
+    for (uint64_t sl : slices) {
+      const uint64_t cap = strict_keys_plan(rq, sl);
+      if (rq == 0 || sl == 0) {
+        if (cap != 0) return san_fail("plan: off expected", rq, sl);
+        continue;
+      }
+      if (cap < kKeySlotsMin || cap > kKeySlotsMax || (cap & (cap - 1)))
+        return san_fail("plan: slots out of range", rq, sl);
+      if (cap >= 2 * kKeySlotsMin && cap / 2 >= 4 * sl) return san_fail("plan: over the slice", rq, sl);
+      if (cap / 2 >= rq && cap > kKeySlotsMin) return san_fail("plan: over the request", rq, sl);
+      const strict_region_t rg = strict_region_plan(sl, cap);
+      if (!(rg.list < rg.keyslot && rg.keyslot < rg.block && rg.block + kTriageBlockBytes <= rg.slots &&
+            rg.slots + 4 * cap <= rg.kflags && rg.kflags + 4 * cap <= rg.ktabs &&
+            rg.ktabs % 256 == 0 && rg.block % 8 == 0 && rg.bytes == rg.ktabs + kKeyTabBytes * cap))
+        return san_fail("region: layout", rq, sl);
+    }
+  // the sequence itself: repeated keys, keys without a slot (64 slots), and the set off
+  uint32_t seed = 12345;
+  auto rnd = [&] { return (uint8_t)((seed = seed * 1664525u + 1013904223u) >> 24); };
+  for (uint32_t n : {1u, 65u, 300u}) {
+    const uint32_t nk = n < 100 ? 3 : 90;
+    std::vector<uint8_t> keys(32 * nk), pks(32 * n), sigs(64 * n), ks(32 * n);
+    for (auto& b : keys) b = rnd();
+    for (uint32_t j = 0; j < n; ++j) {
+      memcpy(&pks[32 * j], &keys[32 * (j % nk)], 32);
+      for (int t = 0; t < 64; ++t) sigs[64 * j + t] = rnd();
+      sigs[64 * j + 63] &= 0x0f;   // s canonical, so the items whose points decode reach the ladder
+      for (int t = 0; t < 32; ++t) ks[32 * j + t] = rnd();
+      ks[32 * j + 31] &= 0x0f;
+    }
+    std::vector<int32_t> off(n), on(n);
+    uint64_t st[3];
+    if (hc_verify_strict_keyset_many(pks.data(), sigs.data(), ks.data(), n, 0, -16, off.data(), nullptr, st))
+      return san_fail("run (off)", n, 0);
+    if (st[0] != 0 || st[1] != 0 || st[2] != n) return san_fail("stats (off)", st[1], st[2]);
+    for (uint64_t slots : {64ull, 65536ull}) {
+      std::vector<uint32_t> ksl(n);
+      if (hc_verify_strict_keyset_many(pks.data(), sigs.data(), ks.data(), n, slots, -16, on.data(), ksl.data(), st))
+        return san_fail("run (on)", n, slots);
+      if (on != off) return san_fail("statuses differ", n, slots);
+      if (st[1] + st[2] != n || st[0] > 32768 || st[1] == 0) return san_fail("stats (on)", st[0], st[1]);
+    }
+  }
+  printf("keyset_san ok\n");
+  return 0;
+}
+#endif

@@ -14,6 +14,13 @@ beyond the spread of one variant's own rounds.
 
 Build knobs of the two-pass path (tools/build_variant.sh NAME "-D..."): NW_TRIAGE_WAVES,
 NW_STRICT_WAVES, NW_PF_SWAP, NW_ADD_NEGC.
+
+A variant may also be a run-time knob of one build: LIB@NAME=VALUE sets that environment
+variable around the variant's launches (knobs read per launch only: NW_STRICT_KEYS, the
+slots of the call's key set, 0 = off; NW_TRIAGE_SLICE), e.g.
+    LIB LIB@NW_STRICT_KEYS=0
+--keys K: the corpus's signers (bench.py's config 4 has 4,096); K = 0: every item has a key
+of its own (then all items are valid: keys and signatures made on the device, no edits).
 """
 import argparse
 import ctypes
@@ -28,6 +35,32 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import bench  # noqa: E402
+
+
+def split_variant(spec):
+    """'LIB' or 'LIB@NAME=VALUE' -> (path, env dict)."""
+    path, _, knob = spec.partition("@")
+    env = {}
+    if knob:
+        k, _, v = knob.partition("=")
+        env[k] = v
+    return path, env
+
+
+def distinct_key_corpus(dev, stream, n, seed):
+    """n valid items, every one under its own key (device keygen and signing)."""
+    from narwhal_amd import _lib
+    L = _lib.lib()
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    seeds = torch.randint(0, 256, (n, 32), dtype=torch.uint8, generator=g).to(dev)
+    msgs = torch.randint(0, 256, (n, 32), dtype=torch.uint8, generator=g).to(dev)
+    pks = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+    bench.check(L.nw_dev_keypair_from_seed_many(bench.ptr(seeds), n, bench.ptr(pks), stream), "keygen")
+    sks = torch.cat([seeds, pks], dim=1).contiguous()
+    sigs = torch.empty((n, 64), dtype=torch.uint8, device=dev)
+    bench.check(L.nw_dev_sign_many(bench.ptr(sks), 64, bench.ptr(msgs), 32, n, bench.ptr(sigs), stream), "sign")
+    torch.cuda.synchronize()
+    return msgs, pks, sigs
 
 
 def load(path):
@@ -51,6 +84,8 @@ def main():
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--all-valid", action="store_true",
                     help="tile only the corpus's valid items (no early-decided statuses)")
+    ap.add_argument("--keys", type=int, default=4096,
+                    help="signers of the corpus; 0 = a key per item (all valid)")
     ap.add_argument("libs", nargs="+")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -60,27 +95,45 @@ def main():
     stream = ctypes.c_void_p(ts.cuda_stream)
     from narwhal_amd import _lib
     assert _lib.lib().nw_init() > 0
-    m_u, p_u, s_u, valid = bench.build_strict_corpus(dev, stream, a.unique, 4096, seed=1000)
     n = a.items
-    if a.all_valid:
-        good = torch.from_numpy(np.nonzero(valid)[0]).to(dev)
-        idx = good[torch.arange(n, dtype=torch.int64, device=dev) % good.numel()]
-        valid = np.ones(good.numel(), dtype=bool)
+    if a.keys == 0:
+        m, p, s = distinct_key_corpus(dev, stream, n, seed=1000)
+        exp = np.ones(n, dtype=bool)
     else:
-        idx = torch.arange(n, dtype=torch.int64, device=dev) % a.unique
-    m, p, s = (t.index_select(0, idx).contiguous() for t in (m_u, p_u, s_u))
-    del idx
-    exp = np.resize(valid, n)
-    libs = [load(x) for x in a.libs]
+        m_u, p_u, s_u, valid = bench.build_strict_corpus(dev, stream, a.unique, a.keys, seed=1000)
+        if a.all_valid:
+            good = torch.from_numpy(np.nonzero(valid)[0]).to(dev)
+            idx = good[torch.arange(n, dtype=torch.int64, device=dev) % good.numel()]
+            valid = np.ones(good.numel(), dtype=bool)
+        else:
+            idx = torch.arange(n, dtype=torch.int64, device=dev) % a.unique
+        m, p, s = (t.index_select(0, idx).contiguous() for t in (m_u, p_u, s_u))
+        del idx
+        exp = np.resize(valid, n)
+    variants = [split_variant(x) for x in a.libs]
+    loaded = {}
+    for path, _ in variants:
+        if path not in loaded:
+            loaded[path] = load(path)
+    libs = [loaded[path] for path, _ in variants]
     st = torch.empty(n, dtype=torch.int32, device=dev)
     bm = torch.zeros((n + 63) // 64 * 8, dtype=torch.uint8, device=dev)
     P = lambda t: ctypes.c_void_p(t.data_ptr())
     times = {x: [] for x in a.libs}
     ok = {}
     for rep in range(a.reps):
-        for name, L in zip(a.libs, libs):
+        for name, L, (_, env) in zip(a.libs, libs, variants):
             def launch():
-                rc = L.nw_dev_verify_strict_many(P(m), 32, P(p), P(s), n, P(st), P(bm), stream)
+                old = {k: os.environ.get(k) for k in env}
+                os.environ.update(env)
+                try:
+                    rc = L.nw_dev_verify_strict_many(P(m), 32, P(p), P(s), n, P(st), P(bm), stream)
+                finally:
+                    for k, v in old.items():
+                        if v is None:
+                            os.environ.pop(k, None)
+                        else:
+                            os.environ[k] = v
                 assert rc == 0, L.nw_last_error()
             launch()
             torch.cuda.synchronize()
