@@ -216,6 +216,12 @@ int nw_path_stats(uint64_t* small_jobs, uint64_t* pipeline_jobs);
  * decompressed and tabulated their own key (all of them under NW_STRICT_KEYS=0). Waits for
  * `stream` (the launch's) first. All zero before the first such launch. */
 int nw_dev_strict_keyset_stats(uint64_t out[3], void* stream);
+/* The same launch's comb check of its hot keys (keys that enough of the call's items share get
+ * 8-bit comb tables for the call; NW_STRICT_COMB=0 turns it off): out[0] = hot keys tabulated
+ * (summed over the slices), out[1] = items checked by the comb, out[2] = items it passed
+ * (status 0 without the ladder), out[3] = items sent on to the triage and the ladder (all of
+ * them when the path is off). Waits for `stream` first. All zero before the first launch. */
+int nw_dev_strict_comb_stats(uint64_t out[4], void* stream);
 
 /* ---- aggregation service: one request per message, coalesced into device jobs ------- */
 /* The front end a crypto-gpu crate puts behind the primary's per-message checks: Core

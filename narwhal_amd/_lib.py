@@ -65,6 +65,7 @@ def lib() -> ctypes.CDLL:
         "nw_dev_sha512_digest32_many": ([P, P, P, S, P, P], I),
         "nw_dev_verify_strict_many": ([P, S, P, P, S, P, P, P], I),
         "nw_dev_strict_keyset_stats": ([P, P], I),
+        "nw_dev_strict_comb_stats": ([P, P], I),
         "nw_keypair_from_seed_many": ([P, S, P], I),
         "nw_sign_many": ([P, S, P, S, S, P], I),
         "nw_dev_keypair_from_seed_many": ([P, S, P, P], I),

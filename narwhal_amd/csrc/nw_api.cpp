@@ -46,6 +46,8 @@ struct SharedDev {
   void* triage_ws = nullptr;   // the two-pass path's slice (grow-only, nw::strict_triage_bytes)
   uint64_t triage_cap = 0;     // items
   uint64_t triage_keys = 0;    // key-set slots the region holds (nw::strict_keys_slots)
+  void* comb_ws = nullptr;     // the hot keys' comb tables (grow-only, nw::strict_comb_bytes)
+  uint64_t comb_slice = 0, comb_slots = 0, comb_keys = 0;   // what it was sized for
   void* ktabs = nullptr;       // committee key tables (grow-only)
   uint32_t* kok = nullptr;
   size_t kcap = 0;             // keys
@@ -297,6 +299,16 @@ int nw_dev_strict_keyset_stats(uint64_t out[3], void* stream) {
   if (rc) return rc;
   if (!out) return set_err(NW_E_INVALID_ARG, "null pointer");
   NW_HIP(nw::strict_keyset_stats(out, pick_stream(stream, c)), "strict key set statistics");
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------
+int nw_dev_strict_comb_stats(uint64_t out[4], void* stream) {
+  DevCtx* c;
+  int rc = begin(&c);
+  if (rc) return rc;
+  if (!out) return set_err(NW_E_INVALID_ARG, "null pointer");
+  NW_HIP(nw::strict_comb_stats(out, pick_stream(stream, c)), "strict comb statistics");
   return 0;
 }
 
@@ -1108,6 +1120,32 @@ int Lease::strict_ws(nw::strict_ws_t* out, size_t n) {
     d.triage_cap = cap;
     d.triage_keys = keys;
   }
+  // the comb check of the launch's hot keys (NW_STRICT_COMB*, read here once per launch): an
+  // allocation of its own, grown like the region; when it cannot be had the launch runs
+  // without the path
+  const nw::strict_comb_plan_t cp = nw::strict_comb_plan(n ? slice : 0, kslots);
+  if (cp.hot_cap && (!d.comb_ws || d.triage_cap > d.comb_slice || d.triage_keys > d.comb_slots ||
+                     cp.hot_cap > d.comb_keys)) {
+    const uint64_t keys = std::max<uint64_t>(cp.hot_cap, d.comb_keys);
+    if (d.comb_ws) {
+      if (d.last_valid) (void)hipEventSynchronize(d.last);
+      (void)hipFree(d.comb_ws);
+    }
+    d.comb_ws = nullptr;
+    d.comb_slice = d.comb_slots = d.comb_keys = 0;
+    if (nw::table_malloc(&d.comb_ws, nw::strict_comb_bytes(d.triage_cap, d.triage_keys, keys)) ==
+        hipSuccess) {
+      d.comb_slice = d.triage_cap;
+      d.comb_slots = d.triage_keys;
+      d.comb_keys = keys;
+    } else {
+      d.comb_ws = nullptr;
+    }
+  }
+  out->comb = cp.hot_cap ? d.comb_ws : nullptr;
+  out->comb_keys_cap = d.comb_keys;
+  out->comb_keys = out->comb ? cp.hot_cap : 0;
+  out->comb_min = cp.min;
   out->base = d.strict_ws;
   out->triage = d.triage_ws;
   out->triage_cap = d.triage_cap;

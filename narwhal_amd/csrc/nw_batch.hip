@@ -2064,18 +2064,23 @@ __global__ __launch_bounds__(256) void k_key_base(const uint32_t* __restrict__ p
                                                   ge* __restrict__ base,
                                                   ge* __restrict__ comb,
                                                   uint32_t* __restrict__ ok,
-                                                  const uint32_t* __restrict__ flag) {
+                                                  const uint32_t* __restrict__ flag,
+                                                  const uint32_t* __restrict__ rows,
+                                                  const uint32_t* __restrict__ nlive) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nkeys || (flag && *flag == 0)) return;   // same committee: tables kept
+  if (nlive && i >= *nlive) return;
+  // rows (launch_key_tables_rows): key i is row rows[i] of pks, and no lambda is computed
+  const uint32_t* key = pks + 8 * (rows ? (uint64_t)rows[i] : i);
   uint32_t Aw[8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) Aw[j] = pks[8 * i + j];
+  for (int j = 0; j < 8; ++j) Aw[j] = key[j];
   ge P;
   const bool dec = ge_frombytes(P, Aw, g_bc.k);
   // lambda: [l] A == [lambda] T8 (l A lies in E[8] for every curve point), by
   // double-and-add over the 253 bits of l — once per key per committee
   uint32_t lam = 0;
-  if (dec) {
+  if (dec && !rows) {
     ge_cached Pc;
     ge_to_cached(Pc, P, g_bc.k.d2);
     ge acc;
@@ -2110,8 +2115,6 @@ __global__ __launch_bounds__(256) void k_key_base(const uint32_t* __restrict__ p
   base[2 * i + 1] = H;
 }
 
-constexpr uint32_t kKeyRun = 64;
-
 NW_HD void put_fe32(uint32_t* w, const fe& f) {
   uint32_t b[8];
   fe_tobytes(b, f);
@@ -2122,13 +2125,16 @@ NW_HD void put_fe32(uint32_t* w, const fe& f) {
 __global__ __launch_bounds__(256) void k_key_tabs(uint64_t nkeys, keyspec ks,
                                                   const ge* __restrict__ comb,
                                                   ge_niels_pad* __restrict__ tabs,
-                                                  const uint32_t* __restrict__ flag) {
+                                                  const uint32_t* __restrict__ flag,
+                                                  uint32_t run,
+                                                  const uint32_t* __restrict__ nlive) {
   const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t N = ks.nent, runs = (N + kKeyRun - 1) / kKeyRun;   // runs per table
+  const uint32_t N = ks.nent, runs = (N + run - 1) / run;   // runs per table
   if (g >= nkeys * keyspec_tables(ks) * runs || (flag && *flag == 0)) return;
   const uint64_t pt = g / runs;   // tables * key + t
-  const uint32_t j0 = (uint32_t)(g % runs) * kKeyRun;
-  const uint32_t cnt = N - j0 < kKeyRun ? N - j0 : kKeyRun;
+  if (nlive && pt / keyspec_tables(ks) >= *nlive) return;
+  const uint32_t j0 = (uint32_t)(g % runs) * run;
+  const uint32_t cnt = N - j0 < run ? N - j0 : run;
   const ge P = comb[pt];
   ge_cached Pc;
   ge_to_cached(Pc, P, g_bc.k.d2);
@@ -2189,6 +2195,7 @@ hipError_t launch_key_tables(const uint32_t* pks, uint64_t nkeys, const keyspec&
                              ge_niels_pad* tabs, uint32_t* ok, hipStream_t stream,
                              uint32_t* saved, uint32_t* flag, bool force) {
   if (nkeys == 0) return hipSuccess;
+  // a committee's tables: 16 / 20 / 24 bits (the small-job kernel holds 16 key digits per slot)
   if (ks.W < 16 || ks.W > kKeyWMax || ks.ntab > 16) return hipErrorInvalidValue;
   ge* base = reinterpret_cast<ge*>(tabs + (uint64_t)ks.tab * nkeys);
   ge* comb = base + 2 * nkeys;
@@ -2197,11 +2204,29 @@ hipError_t launch_key_tables(const uint32_t* pks, uint64_t nkeys, const keyspec&
     hipLaunchKernelGGL(k_key_cmp, dim3(1), dim3(256), 0, stream, pks, saved, nkeys,
                        force ? 1u : 0u, flag);
   hipLaunchKernelGGL(k_key_base, dim3((unsigned)((nkeys + 63) / 64)), dim3(64), 0, stream, pks,
-                     nkeys, ks, base, comb, ok, fl);
+                     nkeys, ks, base, comb, ok, fl, nullptr, nullptr);
   const uint64_t runs = (ks.nent + kKeyRun - 1) / kKeyRun;
   hipLaunchKernelGGL(k_key_tabs,
                      dim3((unsigned)((nkeys * keyspec_tables(ks) * runs + 255) / 256)),
-                     dim3(256), 0, stream, nkeys, ks, comb, tabs, fl);
+                     dim3(256), 0, stream, nkeys, ks, comb, tabs, fl, kKeyRun, nullptr);
+  return hipGetLastError();
+}
+
+hipError_t launch_key_tables_rows(const uint32_t* pks, const uint32_t* rows,
+                                  const uint32_t* nlive, uint64_t ncap, const keyspec& ks,
+                                  ge_niels_pad* tabs, uint32_t* ok, hipStream_t stream) {
+  if (ncap == 0) return hipSuccess;
+  if (!rows || !nlive || keyspec_for(ks.W).W != ks.W) return hipErrorInvalidValue;
+  ge* base = reinterpret_cast<ge*>(tabs + (uint64_t)ks.tab * ncap);
+  ge* comb = base + 2 * ncap;
+  hipLaunchKernelGGL(k_key_base, dim3((unsigned)((ncap + 63) / 64)), dim3(64), 0, stream, pks,
+                     ncap, ks, base, comb, ok, nullptr, rows, nlive);
+  // 129 entries in runs of 43 (64 would split them 64 / 64 / 1)
+  const uint32_t run = ks.W == 8 ? kKeyRun8 : kKeyRun;
+  const uint64_t runs = (ks.nent + run - 1) / run;
+  hipLaunchKernelGGL(k_key_tabs,
+                     dim3((unsigned)((ncap * keyspec_tables(ks) * runs + 255) / 256)),
+                     dim3(256), 0, stream, ncap, ks, comb, tabs, nullptr, run, nlive);
   return hipGetLastError();
 }
 

@@ -87,7 +87,31 @@ struct strict_ws_t {
   uint64_t key_slots_cap = 0; // slots
   uint64_t slice = 0;         // strict_triage_slice(n) of the launch this was handed out for
   uint64_t key_slots = 0;     // strict_keys_slots(slice) of that launch
+  // the comb check of the launch's hot keys (strict_comb_plan; comb == null: off)
+  void* comb = nullptr;       // strict_comb_bytes(triage_cap, key_slots_cap, comb_keys_cap)
+  uint64_t comb_keys_cap = 0; // hot keys the allocation holds
+  uint64_t comb_keys = 0;     // hot_cap of that launch (0: the path is off)
+  uint32_t comb_min = 0;      // uses from which a key is hot
 };
+// The comb check for a call's hot keys (DESIGN.md 5 "Round 9"): a key of the slice's set used
+// by at least NW_STRICT_COMB_MIN items (default 256) that decodes and is not small gets 8-bit
+// comb tables j * 2^(8 t) A (keyspec_for(8): 32 tables of 129 entries, 528 KB) for the call,
+// and its items run keyed_vote_check (additions only, R never decompressed); everything the
+// check does not pass goes through the triage and the ladder as before, from a compacted
+// list. NW_STRICT_COMB=0 turns the path off; hot keys per slice are limited to
+// hot_cap = min(NW_STRICT_COMB_KEYS (default 8192), slice / min). All three are read per
+// launch. The path's allocation (tables, per-slot counts and indices, the to-do list) is
+// apart from the triage region's.
+constexpr uint64_t kCombBlockBytes = 256;
+struct strict_comb_plan_t {
+  uint64_t hot_cap;   // 0: off
+  uint32_t min;
+};
+strict_comb_plan_t strict_comb_plan(uint64_t slice, uint64_t key_slots);
+size_t strict_comb_bytes(uint64_t slice, uint64_t key_slots, uint64_t hot_cap);
+// For the last unkeyed two-pass launch queued on the current device: hot keys tabulated, items
+// checked by the comb, items it passed, items sent on to the triage. Synchronises `stream`.
+hipError_t strict_comb_stats(uint64_t out[4], hipStream_t stream);
 // For the last unkeyed two-pass launch queued on the current device: distinct keys tabulated,
 // items that read a shared table, items on their own path. Synchronises `stream`.
 hipError_t strict_keyset_stats(uint64_t out[3], hipStream_t stream);
@@ -116,9 +140,11 @@ hipError_t upload_batch_consts();
 // the keyed vote chunks' second 8-bit table j * 2^128 A is comb table 128 / W when W divides
 // 128, else one more table built from 2^128 A. W = 16: 16 tables, 67 MB per key; W = 20:
 // 13 + 1 tables, 940 MB per key; W = 24 (NW_KEY_WIDTH=24 only): 11 tables.
-// Only these three widths are built (nw_api.cpp key_width / alloc_key_tables); any other W
-// (e.g. the 0 of a device without tables) is mapped to 16, so that no caller can divide by
-// zero or shift by W - 1 < 0 here, on the host or the device.
+// Only these three widths are built for a committee (nw_api.cpp key_width /
+// alloc_key_tables); W = 8 (32 tables of 129 entries, every digit signed, 528 KB per key) is
+// the width of the call-local tables of a strict launch's hot keys (strict_comb_plan) and of
+// nothing else. Any other W (e.g. the 0 of a device without tables) is mapped to 16, so that
+// no caller can divide by zero or shift by W - 1 < 0 here, on the host or the device.
 #define NW_KS __host__ __device__ __forceinline__
 struct keyspec {
   uint32_t W, ntab, nsigned, nent, tab, half;
@@ -126,7 +152,7 @@ struct keyspec {
 };
 NW_KS constexpr keyspec keyspec_for(uint32_t W) {
   keyspec ks{};
-  if (W != 16 && W != 20 && W != 24) W = 16;
+  if (W != 8 && W != 16 && W != 20 && W != 24) W = 16;
   ks.W = W;
   ks.ntab = (253 + W - 1) / W;
   ks.nsigned = ks.ntab * W > 256 ? ks.ntab - 1 : ks.ntab;
@@ -155,7 +181,8 @@ struct key_tables_t {
   keyspec ks;
 };
 constexpr uint32_t kNoKey = 0xffffffffu;
-constexpr uint32_t kKeyWMax = 24;   // widths 16 / 20 / 24 (at most 16 comb digits)
+constexpr uint32_t kKeyWMax = 24;   // widths 16 / 20 / 24 (at most 16 comb digits), and 8 (32)
+constexpr uint32_t kKeyRun = 64, kKeyRun8 = 43;   // entries per lane of k_key_tabs (129 = 3 x 43)
 // ok[key]: bit 0 = decompressed, bit 1 = small order (8A == identity), bits 2..4 = lambda
 // with [l]A == [lambda]T8 (nw_strict.hpp kKeyLambdaShift: the key's torsion image)
 size_t key_tables_bytes(uint64_t nkeys, const keyspec& ks);
@@ -167,6 +194,12 @@ hipError_t launch_key_tables(const uint32_t* pks, uint64_t nkeys, const keyspec&
                              struct ge_niels_pad* tabs, uint32_t* ok, hipStream_t stream,
                              uint32_t* saved = nullptr, uint32_t* flag = nullptr,
                              bool force = true);
+// The same for keys named by row: key i is pks[8 rows[i]..], i < min(*nlive, ncap) (both read
+// on the device; the grids are sized for ncap). No lambda is computed (ok = decoded / small
+// order only): for the strict check of a call's hot keys, any width keyspec_for builds.
+hipError_t launch_key_tables_rows(const uint32_t* pks, const uint32_t* rows,
+                                  const uint32_t* nlive, uint64_t ncap, const keyspec& ks,
+                                  struct ge_niels_pad* tabs, uint32_t* ok, hipStream_t stream);
 size_t batch_workspace_bytes(uint64_t nbatches, uint64_t nitems);
 // True when launch_verify_batch over these batches (no skip list, no fork) writes its outputs
 // from ONE kernel, the fused tail of a lone large batch: status / fail_index may then be

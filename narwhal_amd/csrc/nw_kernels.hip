@@ -372,9 +372,20 @@ __global__ __launch_bounds__(256, NW_TRIAGE_WAVES) void k_strict_triage(
     const uint32_t* __restrict__ sigs, uint64_t i0, uint64_t ns, int32_t* __restrict__ status,
     uint32_t* __restrict__ xs, uint64_t cap, uint32_t* __restrict__ list,
     uint32_t* __restrict__ count, const uint32_t* __restrict__ keyslot,
-    const uint32_t* __restrict__ kflags) {
-  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const bool active = j < ns;
+    const uint32_t* __restrict__ kflags, const uint32_t* __restrict__ todo,
+    const uint32_t* __restrict__ todo_count, unsigned long long* __restrict__ todo_total,
+    const uint32_t* __restrict__ nhot) {
+  // todo == nullptr, or no hot key in the slice (*nhot == 0: the comb kernels did nothing):
+  // lane q takes item q of the slice; else item todo[q], q < *todo_count (the items the comb
+  // check left undecided, k_strict_todo_list)
+  const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (todo && *nhot == 0) todo = nullptr;
+  const uint64_t nq = todo ? (uint64_t)*todo_count : ns;
+  const bool active = q < nq;
+  // *todo_total += the slice's items that come here (diagnostics, kept over a launch's slices)
+  if (todo_total && q == 0) atomicAdd(todo_total, (unsigned long long)nq);
+  if (__ballot(active) == 0) return;
+  const uint64_t j = todo ? (uint64_t)todo[active ? q : 0] : q;
   const uint64_t i = i0 + (active ? j : 0);
   const strict_src_global src{pks + 8 * i, sigs + 16 * i, msgs + (uint64_t)msg_stride_words * i};
   // the key's slot in the slice's set (keyslot == nullptr: the set is off); an idle lane of the
@@ -430,7 +441,7 @@ struct keyset_atomics {
 __global__ __launch_bounds__(256) void k_strict_keys_probe(
     const uint32_t* __restrict__ pks, uint64_t i0, uint64_t ns, uint32_t* slots, uint32_t cap,
     uint32_t limit, uint32_t* nkeys, uint32_t* __restrict__ keyslot,
-    unsigned long long* __restrict__ with_ctr) {
+    unsigned long long* __restrict__ with_ctr, uint32_t* __restrict__ uses) {
   __shared__ uint32_t s_with[4];
   const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const bool active = j < ns;
@@ -438,6 +449,9 @@ __global__ __launch_bounds__(256) void k_strict_keys_probe(
   if (active) {
     slot = keyset_probe(slots, cap, limit, nkeys, pks, i0, (uint32_t)j, keyset_atomics{});
     keyslot[j] = slot;
+    // uses[slot] += kCombSample for the items of a fixed 1-in-kCombSample sample: an estimate
+    // of the slice's items under that key (the comb path's hot-key choice; nw_strict.hpp)
+    if (uses && slot != kNoSlot && comb_sampled((uint32_t)j)) atomicAdd(uses + slot, kCombSample);
   }
   const uint64_t m = __ballot(slot != kNoSlot);
   if ((threadIdx.x & 63u) == 0) s_with[threadIdx.x >> 6] = (uint32_t)__builtin_popcountll(m);
@@ -459,6 +473,30 @@ __global__ __launch_bounds__(256) void k_strict_keys_build(
   if ((threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(m))
     atomicAdd(stats, (unsigned long long)__builtin_popcountll(m));
   if (owned) keyset_build(slots, s, pks, i0, g_consts.sk, kflags, ktabs);
+}
+
+// The slice's hot keys (comb_key_hot): one lane per slot; a hot slot takes the next dense index
+// while there are fewer than hot_cap (which slots win may differ from run to run, no status
+// does): hotidx[slot] = its index or kNoKey, hotrow[index] = the owner item's row in the slice.
+// *nhot may end above hot_cap; its readers clamp it. cstats[0] += hot keys taken.
+__global__ __launch_bounds__(256) void k_strict_comb_select(
+    const uint32_t* __restrict__ slots, uint32_t cap, const uint32_t* __restrict__ kflags,
+    const uint32_t* __restrict__ uses, uint32_t min_uses, uint32_t hot_cap,
+    uint32_t* __restrict__ nhot, uint32_t* __restrict__ hotidx, uint32_t* __restrict__ hotrow,
+    unsigned long long* __restrict__ cstats) {
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= cap) return;
+  uint32_t h = kNoKey;
+  const uint32_t owner = slots[s];
+  if (owner != 0 && comb_key_hot(uses[s], min_uses, kflags[s])) {
+    const uint32_t t = atomicAdd(nhot, 1u);
+    if (t < hot_cap) {
+      h = t;
+      hotrow[t] = owner - 1;
+      atomicAdd(cstats, 1ull);
+    }
+  }
+  hotidx[s] = h;
 }
 
 // The list's items (persistent, as k_verify_strict): strict_verify_core on the points
@@ -512,14 +550,36 @@ __global__ __launch_bounds__(256, NW_STRICT_WAVES) void k_verify_strict_pre(
 // k_verify_strict in list mode, which names the exact failing check (status 1..7). With
 // honest streams the list is short, so the ~265-squaring decompression of R is skipped
 // for almost every signature.
-__global__ __launch_bounds__(256, NW_KEYED_WAVES) void k_strict_keyed(
+// HOT = false: a committee's tables, item i's key is vote_key[vk0 + i]. HOT = true: the call's
+// hot keys (launch_verify_strict's comb path): vote_key[vk0 + i] is the item's slot in the
+// slice's key set and slotmap[slot] its key's index in the call's 8-bit tables (or kNoKey),
+// valid below *nlive; *checked += items with a key. NW_COMB_WAVES: waves per SIMD of the HOT
+// instance (1 to 4 measured alike on config 4; the LDS prefetcher measured 4 % slower there,
+// as it did for committee tables: DESIGN.md 5 "Round 9").
+#ifndef NW_COMB_WAVES
+#define NW_COMB_WAVES 1
+#endif
+template <bool HOT>
+__global__ __launch_bounds__(256, HOT ? NW_COMB_WAVES : NW_KEYED_WAVES) void k_strict_keyed(
     const uint32_t* __restrict__ msgs, uint32_t msg_stride_words, const uint32_t* __restrict__ pks,
     const uint32_t* __restrict__ sigs, uint64_t i0, uint64_t ns, int32_t* __restrict__ status,
-    key_tables_t keys, const ge_niels_pad* __restrict__ bcomb, vote_planes_t vp) {
+    key_tables_t keys, const ge_niels_pad* __restrict__ bcomb, vote_planes_t vp,
+    uint64_t vk0, const uint32_t* __restrict__ slotmap, const uint32_t* __restrict__ nlive,
+    unsigned long long* __restrict__ checked) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= ns) return;
+  if constexpr (HOT) {
+    if (*nlive == 0) return;   // no hot key: the triage takes the whole slice
+  }
   const uint64_t gi = i0 + i;
-  const uint32_t kk = keys.vote_key[gi];
+  uint32_t kk = keys.vote_key[vk0 + i];
+  if constexpr (HOT) {
+    kk = kk != kNoSlot ? slotmap[kk] : kNoKey;
+    if (kk != kNoKey && kk >= *nlive) kk = kNoKey;
+    const uint64_t m = __ballot(kk != kNoKey);
+    if (m && (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(m))
+      atomicAdd(checked, (unsigned long long)__builtin_popcountll(m));
+  }
   uint32_t st = kVoteFail;
   if (kk != kNoKey) {
     const strict_src_global src{pks + 8 * gi, sigs + 16 * gi,
@@ -544,9 +604,11 @@ __global__ __launch_bounds__(256, NW_KEYED_WAVES) void k_strict_keyed(
 __global__ __launch_bounds__(256) void k_strict_keyed_inv(uint64_t i0, uint64_t ns,
                                                           uint64_t nchunks,
                                                           int32_t* __restrict__ status,
-                                                          vote_planes_t vp) {
+                                                          vote_planes_t vp,
+                                                          const uint32_t* __restrict__ nlive) {
+  // nlive (optional): nothing to do when *nlive == 0 (k_strict_keyed<true> wrote no state)
   const uint64_t lane = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (lane >= nchunks) return;
+  if (lane >= nchunks || (nlive && *nlive == 0)) return;
   auto load = [&](fe& f, int base, uint64_t i) {
 #pragma unroll
     for (int k = 0; k < 10; ++k) f.v[k] = vp.planes[(uint64_t)(base + k) * vp.S + i];
@@ -600,6 +662,49 @@ __global__ __launch_bounds__(256) void k_strict_keyed_list(uint64_t i0, uint64_t
     base = atomicAdd(count, (uint32_t)__popcll(m));
   base = (uint32_t)__shfl((int)base, __ffsll((unsigned long long)m) - 1);
   if (f) list[base + (uint32_t)__popcll(m & ((1ull << lane) - 1))] = (uint32_t)(i0 + i);
+}
+
+// The same for the comb path's to-do list (slice-relative items, in no particular order): a
+// block takes kTodoPer x 256 consecutive items and appends its failed ones with ONE atomic
+// (a slice of 12.5M items with ~10 % of them failed: one atomic per wave was ~195 k
+// same-address atomics, 4.6 ms).
+constexpr uint32_t kTodoPer = 16;
+__global__ __launch_bounds__(256) void k_strict_todo_list(uint64_t ns,
+                                                          const uint32_t* __restrict__ state,
+                                                          uint32_t* __restrict__ list,
+                                                          uint32_t* __restrict__ count,
+                                                          const uint32_t* __restrict__ nlive) {
+  __shared__ uint32_t s_wave[4];
+  __shared__ uint32_t s_base;
+  if (*nlive == 0) return;   // no hot key, no state: the triage takes the whole slice
+  const uint64_t b0 = (uint64_t)blockIdx.x * (256 * kTodoPer);
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  // round r: items b0 + 256 r + threadIdx.x; this wave's failed items of all rounds, counted
+  uint64_t masks[kTodoPer];
+  uint32_t mine = 0;
+#pragma unroll
+  for (uint32_t r = 0; r < kTodoPer; ++r) {
+    const uint64_t i = b0 + 256 * r + threadIdx.x;
+    masks[r] = __ballot(i < ns && state[i] == kVoteFail);
+    mine += (uint32_t)__builtin_popcountll(masks[r]);
+  }
+  if (lane == 0) s_wave[wave] = mine;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint32_t tot = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    s_base = tot ? atomicAdd(count, tot) : 0u;
+  }
+  __syncthreads();
+  uint32_t pos = s_base;
+  for (uint32_t w = 0; w < wave; ++w) pos += s_wave[w];
+#pragma unroll
+  for (uint32_t r = 0; r < kTodoPer; ++r) {
+    const uint64_t m = masks[r];
+    if ((m >> lane) & 1ull)
+      list[pos + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull))] =
+          (uint32_t)(b0 + 256 * r + threadIdx.x);
+    pos += (uint32_t)__builtin_popcountll(m);
+  }
 }
 
 // Verdict bitmap from the statuses (bit i set iff status[i] == 0), 64 items per wave.
@@ -1114,16 +1219,81 @@ size_t strict_triage_bytes(uint64_t slice, uint64_t key_slots) {
   return strict_region_plan(slice, key_slots).bytes;
 }
 
-// Diagnostics of the last unkeyed two-pass launch per device (strict_keyset_stats).
+// The comb path's plan for a launch (nw_kernels.h): the three knobs, read per launch.
+strict_comb_plan_t strict_comb_plan(uint64_t slice, uint64_t key_slots) {
+  strict_comb_plan_t p{0, 256};
+  if (const char* e = getenv("NW_STRICT_COMB"))
+    if (e[0] == '0') return p;
+  if (slice == 0 || key_slots == 0) return p;
+  if (const char* e = getenv("NW_STRICT_COMB_MIN")) {
+    const unsigned long long v = strtoull(e, nullptr, 10);
+    p.min = (uint32_t)std::min<unsigned long long>(std::max<unsigned long long>(v, 1), 1u << 30);
+  }
+  uint64_t keys = 8192;
+  if (const char* e = getenv("NW_STRICT_COMB_KEYS")) keys = strtoull(e, nullptr, 10);
+  p.hot_cap = std::min<uint64_t>({keys, slice / p.min, 1ull << 20});
+  return p;
+}
+// The path's allocation: a kCombBlockBytes block (nhot and the to-do count as words, then the
+// launch's counters: hot keys, items checked, items listed, 64 bits each from byte 8), the
+// to-do list (a word per item of the slice), per slot of the key set its uses and its hot
+// index, per hot key its owner's row and its flags, then the tables (key_tables_bytes).
+namespace {
+struct comb_region_t {
+  uint64_t todo, uses, hotidx, hotrow, hok, tabs, bytes;
+};
+comb_region_t comb_region_plan(uint64_t slice, uint64_t key_slots, uint64_t hot_cap) {
+  comb_region_t r;
+  r.todo = kCombBlockBytes;
+  r.uses = r.todo + 4 * slice;
+  r.hotidx = r.uses + 4 * key_slots;
+  r.hotrow = r.hotidx + 4 * key_slots;
+  r.hok = r.hotrow + 4 * hot_cap;
+  r.tabs = (r.hok + 4 * hot_cap + 255) & ~255ull;
+  r.bytes = r.tabs + key_tables_bytes(hot_cap, keyspec_for(8));
+  return r;
+}
+}  // namespace
+size_t strict_comb_bytes(uint64_t slice, uint64_t key_slots, uint64_t hot_cap) {
+  return comb_region_plan(slice, key_slots, hot_cap).bytes;
+}
+
+// Diagnostics of the last unkeyed two-pass launch per device (strict_keyset_stats,
+// strict_comb_stats).
 namespace {
 struct keyset_record_t {
   const char* dev = nullptr;   // the region's block (strict_region_plan)
   uint64_t n = 0;
   bool valid = false, on = false;
+  const char* comb = nullptr;  // the comb path's block, or null: the path was off
 };
 std::mutex g_keyset_m;
 keyset_record_t g_keyset_last[64];
 }  // namespace
+hipError_t strict_comb_stats(uint64_t out[4], hipStream_t stream) {
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  keyset_record_t rec;
+  {
+    std::lock_guard<std::mutex> g(g_keyset_m);
+    if (dev >= 0 && dev < 64) rec = g_keyset_last[dev];
+  }
+  out[0] = out[1] = out[2] = out[3] = 0;
+  if (!rec.valid) return hipSuccess;
+  e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) return e;
+  out[3] = rec.n;
+  if (!rec.comb) return hipSuccess;
+  unsigned long long h[3];
+  e = hipMemcpy(h, rec.comb + 8, sizeof(h), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return e;
+  out[0] = h[0];
+  out[1] = h[1];
+  out[3] = h[2];
+  out[2] = rec.n - h[2];   // every item is either passed by the comb or listed
+  return hipSuccess;
+}
 hipError_t strict_keyset_stats(uint64_t out[3], hipStream_t stream) {
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
@@ -1165,6 +1335,13 @@ hipError_t launch_verify_strict(const uint32_t* msgs, uint32_t msg_stride_words,
   if (eb == hipSuccess && kt.vote_key) eb = btab_for_current_device(1, &bcomb);
   if (eb != hipSuccess) return eb;
   const char* kf = getenv("NW_STRICT_KEYED_FAST");
+  // the comb check of the call's hot keys needs its allocation (Lease::strict_ws) and the B
+  // comb; without either the launch runs without it
+  bool comb_on = !kt.vote_key && strict_triage_on() && wsp.comb && wsp.comb_keys && wsp.key_slots;
+  if (comb_on && btab_for_current_device(1, &bcomb) != hipSuccess) {
+    comb_on = false;
+    bcomb = nullptr;
+  }
   if (!kt.vote_key && strict_triage_on()) {
     // the slice Lease::strict_ws chose for this launch (one read of NW_TRIAGE_SLICE per launch)
     const uint64_t slice = wsp.slice;
@@ -1189,11 +1366,31 @@ hipError_t launch_verify_strict(const uint32_t* msgs, uint32_t msg_stride_words,
       hipError_t e = hipMemsetAsync(stats, 0, kTriageBlockBytes - 8, stream);
       if (e != hipSuccess) return e;
     }
+    const keyspec ks8 = keyspec_for(8);
+    const uint32_t hot_cap = (uint32_t)wsp.comb_keys;
+    const comb_region_t cg = comb_region_plan(slice, kcap, hot_cap);
+    if (comb_on && (wsp.comb_min == 0 ||
+                    cg.bytes > strict_comb_bytes(wsp.triage_cap, wsp.key_slots_cap, wsp.comb_keys_cap)))
+      return hipErrorInvalidValue;
+    char* const cregion = comb_on ? static_cast<char*>(wsp.comb) : nullptr;
+    uint32_t* const nhot = reinterpret_cast<uint32_t*>(cregion);
+    uint32_t* const tcount = nhot + 1;
+    unsigned long long* const cstats = reinterpret_cast<unsigned long long*>(cregion + 8);
+    uint32_t* const todo = reinterpret_cast<uint32_t*>(cregion + cg.todo);
+    uint32_t* const uses = comb_on ? reinterpret_cast<uint32_t*>(cregion + cg.uses) : nullptr;
+    uint32_t* const hotidx = reinterpret_cast<uint32_t*>(cregion + cg.hotidx);
+    uint32_t* const hotrow = reinterpret_cast<uint32_t*>(cregion + cg.hotrow);
+    uint32_t* const hok = reinterpret_cast<uint32_t*>(cregion + cg.hok);
+    ge_niels_pad* const htabs = reinterpret_cast<ge_niels_pad*>(cregion + cg.tabs);
+    if (comb_on) {
+      hipError_t e = hipMemsetAsync(cstats, 0, kCombBlockBytes - 8, stream);
+      if (e != hipSuccess) return e;
+    }
     {
       int dev = 0;
       if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
         std::lock_guard<std::mutex> g(g_keyset_m);
-        g_keyset_last[dev] = keyset_record_t{region + rg.block, n, true, kcap != 0};
+        g_keyset_last[dev] = keyset_record_t{region + rg.block, n, true, kcap != 0, cregion};
       }
     }
     // equal slices of at most `slice` items
@@ -1207,14 +1404,42 @@ hipError_t launch_verify_strict(const uint32_t* msgs, uint32_t msg_stride_words,
         // the slice's key set: each key's slot, then each slot's flags and table, once
         e = hipMemsetAsync(kslots, 0, 4 * (size_t)kcap, stream);
         if (e != hipSuccess) return e;
+        if (comb_on) {
+          e = hipMemsetAsync(nhot, 0, 8, stream);   // nhot and the to-do count
+          if (e == hipSuccess) e = hipMemsetAsync(uses, 0, 4 * (size_t)kcap, stream);
+          if (e != hipSuccess) return e;
+        }
         hipLaunchKernelGGL(k_strict_keys_probe, dim3(grid_for(ns, 256)), dim3(256), 0, stream,
-                           pks, i0, ns, kslots, kcap, kcap / 2, nkeys, keyslot, with_ctr);
+                           pks, i0, ns, kslots, kcap, kcap / 2, nkeys, keyslot, with_ctr, uses);
         hipLaunchKernelGGL(k_strict_keys_build, dim3(grid_for(kcap, 256)), dim3(256), 0, stream,
                            pks, i0, kslots, kcap, kflags, ktabs, stats);
       }
+      if (comb_on) {
+        // the slice's hot keys and their 8-bit comb tables, then the comb check of their items:
+        // a pass is status 0 (k_strict_keyed, or k_strict_keyed_inv for the x parity); every
+        // other item of the slice goes on the to-do list. X' / Z' and the state use the
+        // region's planes 0-20, which the triage overwrites afterwards.
+        hipLaunchKernelGGL(k_strict_comb_select, dim3(grid_for(kcap, 256)), dim3(256), 0, stream,
+                           kslots, kcap, kflags, uses, wsp.comb_min, hot_cap, nhot, hotidx, hotrow,
+                           cstats);
+        hipError_t e2 = launch_key_tables_rows(pks + 8 * i0, hotrow, nhot, hot_cap, ks8, htabs, hok,
+                                               stream);
+        if (e2 != hipSuccess) return e2;
+        const vote_planes_t vp{xs, xs + 20 * slice, slice, nullptr};
+        const key_tables_t hk{htabs, hok, keyslot, ks8};
+        hipLaunchKernelGGL(k_strict_keyed<true>, dim3(grid_for(ns, 256)), dim3(256), 0, stream,
+                           msgs, msg_stride_words, pks, sigs, i0, ns, status, hk, bcomb, vp, 0,
+                           hotidx, nhot, cstats + 1);
+        const uint64_t nchunks = std::min<uint64_t>(ns, 256ull * 4 * 2 * 64);
+        hipLaunchKernelGGL(k_strict_keyed_inv, dim3(grid_for(nchunks, 256)), dim3(256), 0, stream,
+                           i0, ns, nchunks, status, vp, nhot);
+        hipLaunchKernelGGL(k_strict_todo_list, dim3(grid_for(ns, 256 * kTodoPer)), dim3(256), 0,
+                           stream, ns, vp.state, todo, tcount, nhot);
+      }
       hipLaunchKernelGGL(k_strict_triage, dim3(grid_for(ns, 256)), dim3(256), 0, stream, msgs,
                          msg_stride_words, pks, sigs, i0, ns, status, xs, slice, list, count,
-                         keyslot, kflags);
+                         keyslot, kflags, comb_on ? todo : nullptr, tcount,
+                         comb_on ? cstats + 2 : nullptr, nhot);
       hipLaunchKernelGGL(k_verify_strict_pre,
                          dim3(std::min<uint64_t>(strict_grid(), grid_for(ns, 256))), dim3(256),
                          0, stream, msgs, msg_stride_words, pks, sigs, i0, list, count, xs,
@@ -1248,11 +1473,12 @@ hipError_t launch_verify_strict(const uint32_t* msgs, uint32_t msg_stride_words,
     const uint64_t ns = std::min(S, n - i0);
     hipError_t e = hipMemsetAsync(count, 0, 4, stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_strict_keyed, dim3(grid_for(ns, 256)), dim3(256), 0, stream, msgs,
-                       msg_stride_words, pks, sigs, i0, ns, status, kt, bcomb, vp);
+    hipLaunchKernelGGL(k_strict_keyed<false>, dim3(grid_for(ns, 256)), dim3(256), 0, stream, msgs,
+                       msg_stride_words, pks, sigs, i0, ns, status, kt, bcomb, vp, i0, nullptr,
+                       nullptr, nullptr);
     const uint64_t nchunks = std::min<uint64_t>(ns, 256ull * 4 * 2 * 64);
     hipLaunchKernelGGL(k_strict_keyed_inv, dim3(grid_for(nchunks, 256)), dim3(256), 0, stream,
-                       i0, ns, nchunks, status, vp);
+                       i0, ns, nchunks, status, vp, nullptr);
     hipLaunchKernelGGL(k_strict_keyed_list, dim3(grid_for(ns, 256)), dim3(256), 0, stream, i0,
                        ns, vp.state, list, count);
     // the leftovers: full verification (exact status codes), the tables over the planes

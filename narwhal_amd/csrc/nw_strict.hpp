@@ -296,6 +296,20 @@ NW_HD void keyset_build(const uint32_t* slots, uint32_t s, const uint32_t* pks, 
   if (ok) build_table8(ktabs + 8 * (uint64_t)s, P, K.k.d2);
 }
 
+// A key of the set is hot for the comb check (nw_kernels.h strict_comb_plan) when enough items of
+// the slice use it to pay for its 8-bit comb tables and it can pass at all: a key that does
+// not decode or has small order never does.
+// A key's uses are estimated from a fixed sample of the slice's items, one in kCombSample,
+// chosen by a multiplicative hash of the item's index in the slice (so that signers taking
+// turns with a period that divides the sampling interval are still all seen) and scaled: an
+// exact count is 12.5M atomics over a few thousand addresses, ~1 ms a call. The estimate only
+// decides which keys get tables, never a status.
+constexpr uint32_t kCombSample = 16;
+NW_HD bool comb_sampled(uint32_t j) { return ((j * 0x9e3779b1u) >> 28) == 0; }
+NW_HD bool comb_key_hot(uint32_t uses, uint32_t min_uses, uint32_t keyflags) {
+  return uses >= min_uses && (keyflags & kKeyDecoded) != 0 && (keyflags & kKeySmall) == 0;
+}
+
 // Inputs of one strict verification, fetched when needed (so nothing but the decompression
 // is live across the decompression): A(w) / R(w) / S(w) give the 8 LE words of the public
 // key, of R and of s; k(x) gives k = H(R || A || M) mod l. The kernel's source reloads

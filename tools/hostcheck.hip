@@ -3,6 +3,8 @@
 // point / scalar / ladder code the kernels run against the CPU oracle, without a GPU.
 // SHA-512 is device-only, so the verification entry takes k = H(R||A||M) mod l as input.
 #include <string.h>
+#include <algorithm>
+#include <vector>
 #include "../narwhal_amd/csrc/nw_consts.hpp"
 #include "../narwhal_amd/csrc/nw_ladder.hpp"
 
@@ -333,11 +335,11 @@ int hc_key_lambda(const uint8_t pk[32]) {
   return (f & kKeyDecoded) ? (int)((f & kKeyLambdaMask) >> kKeyLambdaShift) : -1;
 }
 
-// Comb width of the keyed checks' (lazily computed) key tables: 16 or 20 (the widths the
-// device builds, nw_api.cpp key_width).
+// Comb width of the keyed checks' (lazily computed) key tables: 16, 20 or 24 (the widths the
+// device builds for a committee, nw_api.cpp key_width) or 8 (a strict launch's hot keys).
 static uint32_t g_key_w = 16;
 int hc_set_key_width(int w) {
-  if (w != 16 && w != 20 && w != 24) return -1;
+  if (w != 8 && w != 16 && w != 20 && w != 24) return -1;
   g_key_w = (uint32_t)w;
   return 0;
 }
@@ -466,6 +468,90 @@ int hc_verify_strict_keyset_many(const uint8_t* pks, const uint8_t* sigs, const 
   free(mem);
   return 0;
 }
+// A slice the way launch_verify_strict runs it with the comb check of the hot keys: the key
+// set's probe with the sampled use counts, the slots' flags and tables, the hot keys in slot
+// order up to comb_keys (the device hands out its indices by atomic ticket), keyed_vote_check
+// with the hot key's 8-bit comb (keytab_lazy, no lambda: the flags are kKeyDecoded alone) and
+// the parity by one inversion per item, then everything that did not pass through
+// keyset_item. comb_min = 0 turns the path off. stats: hot keys, items checked, items passed,
+// items sent on.
+int hc_verify_strict_comb_many(const uint8_t* pks, const uint8_t* sigs, const uint8_t* k32,
+                               uint32_t n, uint64_t key_slots, int bw, uint32_t comb_min,
+                               uint32_t comb_keys, int32_t* status_out, uint64_t stats[4]) {
+  init();
+  if (n == 0) return 0;
+  const uint64_t slice = ((uint64_t)n + 63) & ~63ull;
+  const uint32_t cap = (uint32_t)strict_keys_plan(key_slots, slice);
+  std::vector<uint32_t> keyslot(n), slots(cap), kflags(cap), uses(cap), hotidx(cap, kNoKey);
+  std::vector<ge_cached_pk> ktabs(8 * (size_t)cap);
+  std::vector<uint32_t> pkw(8 * (size_t)n);
+  memcpy(pkw.data(), pks, 32 * (size_t)n);
+  uint32_t nkeys = 0;
+  for (uint32_t j = 0; j < n; ++j) {
+    keyslot[j] = cap ? keyset_probe(slots.data(), cap, cap / 2, &nkeys, pkw.data(), 0, j,
+                                    plain_atomics{})
+                     : kNoSlot;
+    if (keyslot[j] != kNoSlot && comb_sampled(j)) uses[keyslot[j]] += kCombSample;
+  }
+  for (uint32_t s = 0; s < cap; ++s)
+    keyset_build(slots.data(), s, pkw.data(), 0, SK, kflags.data(), ktabs.data());
+  const uint64_t hot_cap = comb_min ? std::min<uint64_t>(comb_keys, slice / comb_min) : 0;
+  std::vector<ge> hotA;
+  for (uint32_t s = 0; s < cap && hotA.size() < hot_cap; ++s) {
+    if (slots[s] == 0 || !comb_key_hot(uses[s], comb_min, kflags[s])) continue;
+    ge A;
+    if (!ge_frombytes(A, pkw.data() + 8 * (size_t)(slots[s] - 1), K)) return -2;
+    hotidx[s] = (uint32_t)hotA.size();
+    hotA.push_back(A);
+  }
+  uint64_t checked = 0, passed = 0;
+  const keyspec ks8 = keyspec_for(8);
+  for (uint32_t j = 0; j < n; ++j) {
+    uint32_t Aw[8], Rw[8], Sw[8], kw[8];
+    load8(Aw, pks + 32 * (size_t)j); load8(Rw, sigs + 64 * (size_t)j);
+    load8(Sw, sigs + 64 * (size_t)j + 32); load8(kw, k32 + 32 * (size_t)j);
+    const uint32_t h = keyslot[j] != kNoSlot ? hotidx[keyslot[j]] : kNoKey;
+    if (h != kNoKey) {
+      ++checked;
+      const strict_src_arrays src{Aw, Rw, Sw, kw};
+      fe X, Z;
+      uint32_t st = keyed_vote_check(src, SK, bcomb_lazy{BT, &SK.k.d2},
+                                     keytab_lazy{&hotA[h], &SK.k.d2, ks8}, kKeyDecoded, X, Z);
+      if (st >= kVotePending) {
+        fe zi, x;
+        fe_invert(zi, Z);
+        fe_mul(x, X, zi);
+        st = fe_isnegative(x) == (st & 1) ? kVotePass : kVoteFail;
+      }
+      if (st == kVotePass) {
+        status_out[j] = NW_OK;
+        ++passed;
+        continue;
+      }
+    }
+    src_arrays_keys src{};
+    src.a = Aw; src.r = Rw; src.s = Sw; src.k = kw;
+    src.ktabs = ktabs.data();
+    status_out[j] = bw == -24
+        ? keyset_item<24>(src, btab_lazy_entry{{BT, &SK.k.d2}, {}}, keyslot[j], kflags.data())
+        : keyset_item<16>(src, btab_wide{BTW, BTW_N}, keyslot[j], kflags.data());
+  }
+  if (stats) { stats[0] = hotA.size(); stats[1] = checked; stats[2] = passed; stats[3] = n - passed; }
+  return 0;
+}
+
+// k's digits at comb width w (key_recode / key_digit): digits[t], t < ntab; returns ntab.
+int hc_key_digits(const uint8_t k32[32], int w, int32_t digits[32]) {
+  const keyspec ks = keyspec_for((uint32_t)w);
+  if (ks.W != (uint32_t)w) return -1;
+  sc k;
+  load8(k.w, k32);
+  uint32_t kd[8];
+  key_recode(kd, k, ks);
+  for (uint32_t t = 0; t < ks.ntab; ++t) digits[t] = key_digit(kd, (int)t, ks);
+  return (int)ks.ntab;
+}
+
 // The documented hash of a key (nw_strict.hpp keyset_hash), for the tests' numpy restatement.
 uint32_t hc_keyset_hash(const uint8_t pk[32]) {
   uint32_t w[8];
