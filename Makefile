@@ -84,8 +84,9 @@ stagesan: tools/stage_san
 tools/stage_san: tools/stagecheck.hip $(CSRC)/nw_stage.hpp include/narwhal_amd.h
 	g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -DSTAGECHECK_MAIN -Iinclude -x c++ $< -o $@
 
-# the key set's sizing, region planning and probe / build / triage / ladder sequence
-# (nw_kernels.h, nw_strict.hpp) under AddressSanitizer / UBSan, as a stand-alone CPU program
+# the key set's sizing, region planning and probe / build / triage / ladder sequence, and the
+# registered signers' hash table and one slice through it (nw_kernels.h, nw_strict.hpp;
+# tools/hostcheck.hip's main) under AddressSanitizer / UBSan, as a stand-alone CPU program
 # (not part of `all`; the instrumented field arithmetic takes about ten minutes to compile):
 # make keysetsan && tools/keyset_san
 keysetsan: tools/keyset_san

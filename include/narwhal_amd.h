@@ -222,6 +222,31 @@ int nw_dev_strict_keyset_stats(uint64_t out[3], void* stream);
  * (status 0 without the ladder), out[3] = items sent on to the triage and the ladder (all of
  * them when the path is off). Waits for `stream` first. All zero before the first launch. */
 int nw_dev_strict_comb_stats(uint64_t out[4], void* stream);
+/* Registered signers: keys that sign most of what a caller sends (a network's primaries, workers
+ * and clients) keep their 8-bit comb tables (528 KB per key) on the device across calls, so
+ * their items take the comb check in every unkeyed strict launch, whatever its size
+ * (nw_signature_verify, nw_verify_strict_many, nw_submit_verify_strict, the strict jobs of the
+ * service and nw_dev_verify_strict_many alike). No status, index or bitmap bit depends on the
+ * set; with nothing registered (the default) every launch is the sequence it was before.
+ *
+ * Replaces the calling thread's device's registered signer set (every device under
+ * NW_ALL_DEVICES) with the n keys at pks (n x 32 bytes, copied). n = 0 clears it. Blocks until
+ * the tables are built; waits for every strict launch queued on the device first. Duplicates
+ * are kept once. A key is its 32 bytes: two encodings of one point are two keys. A key that
+ * does not decode or has small order may be registered but is never used. More than
+ * NW_STRICT_SIGNERS_MAX keys (default 8192: 4.3 GB; read at the call): NW_E_INVALID_ARG.
+ * NW_E_OUT_OF_MEMORY leaves the set empty and the library usable. A launch of fewer than
+ * NW_STRICT_SIGNERS_MIN_ITEMS items (default 1; read per launch) ignores the set, as does every
+ * launch under NW_STRICT_COMB=0. */
+int nw_strict_signers_set(const uint8_t* pks, size_t n);
+/* Registered keys on the current device. */
+int nw_strict_signers_count(uint64_t* n);
+/* For the last unkeyed two-pass launch queued on the current device: out[0] = registered keys
+ * that occurred in it (summed over its slices), out[1] = items checked under them, out[2] =
+ * items the comb passed under them. Synchronises `stream`. Tests and tools only, like
+ * nw_dev_strict_comb_stats, whose out[0] keeps counting call-local tables only and whose
+ * out[1..3] count items whichever tables served them. */
+int nw_dev_strict_signers_stats(uint64_t out[3], void* stream);
 
 /* ---- aggregation service: one request per message, coalesced into device jobs ------- */
 /* The front end a crypto-gpu crate puts behind the primary's per-message checks: Core

@@ -31,7 +31,8 @@ from ._lib import EngineError, check
 __all__ = ["Digest", "Hash", "PublicKey", "SecretKey", "Signature", "CryptoError",
            "EngineError", "generate_keypair", "keypair_from_seed_many", "sign_many",
            "sha512_digest", "sha512_digest32_many", "verify_strict_many",
-           "verify_batch_many"]
+           "verify_batch_many", "set_strict_signers", "strict_signers_count",
+           "strict_signers_stats"]
 
 
 class CryptoError(Exception):
@@ -241,6 +242,39 @@ def verify_strict_many(digests: np.ndarray, pks: np.ndarray, sigs: np.ndarray,
                                                _ptr(pks), _ptr(sigs), n, _ptr(st), _ptr(bm)),
               "nw_verify_strict_many")
     return st, bm
+
+
+def set_strict_signers(keys) -> None:
+    """Replace the current device's registered signers (nw_strict_signers_set): keys that sign
+    most of what will be verified keep their comb tables on the device across calls. ``keys`` is
+    an iterable of PublicKey or an n x 32 uint8 array; an empty one clears the set. No verdict
+    depends on it."""
+    if isinstance(keys, np.ndarray):
+        arr = np.ascontiguousarray(keys, dtype=np.uint8).reshape(-1, 32)
+    else:
+        raw = [k.value if isinstance(k, PublicKey) else bytes(k) for k in keys]
+        if any(len(r) != 32 for r in raw):
+            raise ValueError("a public key is 32 bytes")
+        arr = np.frombuffer(b"".join(raw), np.uint8).reshape(-1, 32)
+    check(_lib.lib().nw_strict_signers_set(_ptr(arr) if len(arr) else None, len(arr)),
+          "nw_strict_signers_set")
+
+
+def strict_signers_count() -> int:
+    """Registered keys on the current device."""
+    n = ctypes.c_uint64(0)
+    check(_lib.lib().nw_strict_signers_count(ctypes.byref(n)), "nw_strict_signers_count")
+    return n.value
+
+
+def strict_signers_stats(stream=None) -> tuple[int, int, int]:
+    """(registered keys that occurred, items checked under them, items the comb passed under
+    them) of the last unkeyed strict launch on the current device; waits for ``stream`` (a raw
+    stream handle; None = the calling thread's own). Tests and tools only."""
+    out = (ctypes.c_uint64 * 3)()
+    check(_lib.lib().nw_dev_strict_signers_stats(out, ctypes.c_void_p(stream)),
+          "nw_dev_strict_signers_stats")
+    return int(out[0]), int(out[1]), int(out[2])
 
 
 def verify_batch_many(digests: np.ndarray, pks: np.ndarray, sigs: np.ndarray,

@@ -48,6 +48,8 @@ struct SharedDev {
   uint64_t triage_keys = 0;    // key-set slots the region holds (nw::strict_keys_slots)
   void* comb_ws = nullptr;     // the hot keys' comb tables (grow-only, nw::strict_comb_bytes)
   uint64_t comb_slice = 0, comb_slots = 0, comb_keys = 0;   // what it was sized for
+  nw::strict_signers_t signers;   // the registered signers: an allocation of their own, which
+                                  // no growth of the triage or comb regions touches
   void* ktabs = nullptr;       // committee key tables (grow-only)
   uint32_t* kok = nullptr;
   size_t kcap = 0;             // keys
@@ -309,6 +311,71 @@ int nw_dev_strict_comb_stats(uint64_t out[4], void* stream) {
   if (rc) return rc;
   if (!out) return set_err(NW_E_INVALID_ARG, "null pointer");
   NW_HIP(nw::strict_comb_stats(out, pick_stream(stream, c)), "strict comb statistics");
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------
+// The registered signers of a device (DESIGN.md 5 "Round 10").
+namespace {
+int signers_set_on(int dev, const uint8_t* keys32, size_t n) {
+  int rc = activate(dev);
+  if (rc) return rc;
+  DevCtx& c = t_state.ctx[dev];
+  if (!c.stream) {
+    hipError_t e = hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking);
+    if (e != hipSuccess) return set_err(NW_E_DEVICE, "hipStreamCreate", e);
+  }
+  nw::rt::Lease lease;
+  rc = lease.acquire(dev, c.stream);
+  if (!rc) rc = lease.signers_set(keys32, n);   // returns with the tables built
+  const int rc2 = lease.release();   // later launches wait on this event
+  return rc ? rc : rc2;
+}
+}  // namespace
+
+int nw_strict_signers_set(const uint8_t* pks, size_t n) {
+  int rc = ensure_init();
+  if (rc) return rc;
+  const int dev = t_state.device;
+  if (dev != NW_ALL_DEVICES && (dev < 0 || dev >= g_ndev))
+    return set_err(NW_E_INVALID_ARG, "bad device index");
+  if (n && !pks) return set_err(NW_E_INVALID_ARG, "null pointer");
+  if (n > nw::strict_signers_max())
+    return set_err(NW_E_INVALID_ARG, "more keys than NW_STRICT_SIGNERS_MAX (default 8192)");
+  // duplicates are kept once, in the order of their first occurrence
+  std::vector<uint8_t> keys;
+  keys.reserve(32 * n);
+  {
+    std::unordered_map<std::string, int> seen;
+    for (size_t i = 0; i < n; ++i)
+      if (seen.emplace(std::string(reinterpret_cast<const char*>(pks + 32 * i), 32), 0).second)
+        keys.insert(keys.end(), pks + 32 * i, pks + 32 * i + 32);
+  }
+  for (int d = dev == NW_ALL_DEVICES ? 0 : dev; d < (dev == NW_ALL_DEVICES ? g_ndev : dev + 1);
+       ++d) {
+    rc = signers_set_on(d, keys.data(), keys.size() / 32);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+int nw_strict_signers_count(uint64_t* n) {
+  DevCtx* c;
+  int rc = begin(&c);
+  if (rc) return rc;
+  if (!n) return set_err(NW_E_INVALID_ARG, "null pointer");
+  SharedDev& d = g_shared[t_state.device];
+  std::lock_guard<std::mutex> g(d.m);
+  *n = d.signers.n;
+  return 0;
+}
+
+int nw_dev_strict_signers_stats(uint64_t out[3], void* stream) {
+  DevCtx* c;
+  int rc = begin(&c);
+  if (rc) return rc;
+  if (!out) return set_err(NW_E_INVALID_ARG, "null pointer");
+  NW_HIP(nw::strict_signers_stats(out, pick_stream(stream, c)), "strict signers statistics");
   return 0;
 }
 
@@ -1124,7 +1191,10 @@ int Lease::strict_ws(nw::strict_ws_t* out, size_t n) {
   // allocation of its own, grown like the region; when it cannot be had the launch runs
   // without the path
   const nw::strict_comb_plan_t cp = nw::strict_comb_plan(n ? slice : 0, kslots);
-  if (cp.hot_cap && (!d.comb_ws || d.triage_cap > d.comb_slice || d.triage_keys > d.comb_slots ||
+  // the registered signers: with any, the path is planned even without room for a call-local
+  // table (a slice below NW_STRICT_COMB_MIN), from NW_STRICT_SIGNERS_MIN_ITEMS items on
+  const bool reg = cp.on && d.signers.n != 0 && n >= nw::strict_signers_min_items();
+  if ((cp.hot_cap || reg) && (!d.comb_ws || d.triage_cap > d.comb_slice || d.triage_keys > d.comb_slots ||
                      cp.hot_cap > d.comb_keys)) {
     const uint64_t keys = std::max<uint64_t>(cp.hot_cap, d.comb_keys);
     if (d.comb_ws) {
@@ -1142,10 +1212,11 @@ int Lease::strict_ws(nw::strict_ws_t* out, size_t n) {
       d.comb_ws = nullptr;
     }
   }
-  out->comb = cp.hot_cap ? d.comb_ws : nullptr;
+  out->comb = cp.hot_cap || reg ? d.comb_ws : nullptr;
   out->comb_keys_cap = d.comb_keys;
   out->comb_keys = out->comb ? cp.hot_cap : 0;
   out->comb_min = cp.min;
+  out->signers = out->comb && reg ? d.signers : nw::strict_signers_t{};
   out->base = d.strict_ws;
   out->triage = d.triage_ws;
   out->triage_cap = d.triage_cap;
@@ -1153,6 +1224,22 @@ int Lease::strict_ws(nw::strict_ws_t* out, size_t n) {
   out->slice = n ? slice : 0;
   out->key_slots = kslots;
   return 0;
+}
+
+int Lease::signers_set(const uint8_t* keys32, size_t n) {
+  SharedDev& d = g_shared[dev_];
+  // a writer: every queued strict launch on the device is ordered before d.last, and the
+  // holder's stream already waits for it; the old tables are freed only once they are idle
+  if (d.last_valid) (void)hipEventSynchronize(d.last);
+  nw::strict_signers_free(&d.signers);
+  const hipError_t e = nw::strict_signers_build(keys32, (uint32_t)n, &d.signers, stream_);
+  if (e == hipSuccess) return 0;
+  (void)hipGetLastError();
+  if (e == hipErrorOutOfMemory)
+    return ::set_err(NW_E_OUT_OF_MEMORY, "hipMalloc (registered signers' tables)", e);
+  if (e == hipErrorInvalidValue)
+    return ::set_err(NW_E_INVALID_ARG, "registered signers: more than 8 keys share one hash");
+  return ::set_err(NW_E_DEVICE, "registered signers: table build", e);
 }
 
 // Comb width of a committee's key tables: 20 bits (13 tables, 940 MB per key: three fewer

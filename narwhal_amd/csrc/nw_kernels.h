@@ -80,6 +80,35 @@ inline strict_region_t strict_region_plan(uint64_t slice, uint64_t key_slots) {
   return r;
 }
 size_t strict_triage_bytes(uint64_t slice, uint64_t key_slots);
+// The device's registered signers (DESIGN.md 5 "Round 10", nw_strict.hpp signers_lookup): n
+// distinct keys whose 8-bit comb tables (keyspec_for(8), identity rows, no lambda: the layout
+// and flags of a launch's call-local tables) are kept until the set is replaced, in one
+// allocation of their own (base). Their items take the comb check whatever the launch's size;
+// a registered key that does not decode or has small order is never matched.
+struct strict_signers_t {
+  void* base = nullptr;
+  const uint32_t* keys = nullptr;    // n x 8 words
+  const uint32_t* slots = nullptr;   // cap words: row + 1 or 0
+  const uint32_t* ok = nullptr;      // n flag words (kKeyDecoded, kKeySmall)
+  const struct ge_niels_pad* tabs = nullptr;
+  uint32_t n = 0, cap = 0;
+};
+// Builds the registry of the n distinct keys at keys32 (host memory, 32 bytes each) on the
+// current device: allocates (table_malloc), uploads the keys and the host-built hash table and
+// queues the table build on `stream`; the host buffers are free once it returns. n = 0 gives the
+// empty registry. hipErrorInvalidValue when no hash table holds the keys (more than kKeyProbes
+// keys of one hash); on any error *out is empty and nothing is left allocated.
+hipError_t strict_signers_build(const uint8_t* keys32, uint32_t n, strict_signers_t* out,
+                                hipStream_t stream);
+void strict_signers_free(strict_signers_t* sg);
+// Registered keys a device takes (NW_STRICT_SIGNERS_MAX, default 8192: 4.3 GB of tables) and the
+// items from which a launch uses them (NW_STRICT_SIGNERS_MIN_ITEMS); both read at the call.
+uint64_t strict_signers_max();
+uint64_t strict_signers_min_items();
+// For the last unkeyed two-pass launch queued on the current device: registered keys that
+// occurred in it (summed over its slices), items checked under them, items the comb passed under
+// them. Synchronises `stream`.
+hipError_t strict_signers_stats(uint64_t out[3], hipStream_t stream);
 struct strict_ws_t {
   void* base = nullptr;       // strict_workspace_bytes()
   void* triage = nullptr;     // strict_triage_bytes(triage_cap, key_slots_cap), or null (keyed)
@@ -90,8 +119,9 @@ struct strict_ws_t {
   // the comb check of the launch's hot keys (strict_comb_plan; comb == null: off)
   void* comb = nullptr;       // strict_comb_bytes(triage_cap, key_slots_cap, comb_keys_cap)
   uint64_t comb_keys_cap = 0; // hot keys the allocation holds
-  uint64_t comb_keys = 0;     // hot_cap of that launch (0: the path is off)
+  uint64_t comb_keys = 0;     // hot_cap of that launch (0: no call-local tables)
   uint32_t comb_min = 0;      // uses from which a key is hot
+  strict_signers_t signers;   // the device's registered signers for that launch (n == 0: none)
 };
 // The comb check for a call's hot keys (DESIGN.md 5 "Round 9"): a key of the slice's set used
 // by at least NW_STRICT_COMB_MIN items (default 256) that decodes and is not small gets 8-bit
@@ -102,10 +132,12 @@ struct strict_ws_t {
 // hot_cap = min(NW_STRICT_COMB_KEYS (default 8192), slice / min). All three are read per
 // launch. The path's allocation (tables, per-slot counts and indices, the to-do list) is
 // apart from the triage region's.
-constexpr uint64_t kCombBlockBytes = 256;
+constexpr uint64_t kCombBlockBytes = 2048;
+constexpr uint32_t kCombStatLanes = 32;
 struct strict_comb_plan_t {
-  uint64_t hot_cap;   // 0: off
+  uint64_t hot_cap;   // 0: no call-local tables (the path is off, or the slice is below min)
   uint32_t min;
+  bool on = false;    // NW_STRICT_COMB is not 0 and the launch has a key set
 };
 strict_comb_plan_t strict_comb_plan(uint64_t slice, uint64_t key_slots);
 size_t strict_comb_bytes(uint64_t slice, uint64_t key_slots, uint64_t hot_cap);

@@ -19,6 +19,7 @@
 #include "nw_consts.hpp"
 
 #include <stdlib.h>
+#include <string.h>
 
 #include <algorithm>
 #include <atomic>
@@ -475,25 +476,61 @@ __global__ __launch_bounds__(256) void k_strict_keys_build(
   if (owned) keyset_build(slots, s, pks, i0, g_consts.sk, kflags, ktabs);
 }
 
+// The slice's keys that are registered signers (nw_strict.hpp signers_lookup): one lane per slot
+// of the slice's key set; an owned slot whose key decodes and is not small looks its owner's 32
+// bytes up in the registry: match[slot] = the registry row or kNoKey. The work is per distinct
+// key, not per item. *nlive += matched slots (the slice's comb kernels run when it is not 0),
+// *matched += the same (diagnostics), one atomic each per wave that has any.
+__global__ __launch_bounds__(256) void k_strict_signers_match(
+    const uint32_t* __restrict__ pks, uint64_t i0, const uint32_t* __restrict__ slots, uint32_t cap,
+    const uint32_t* __restrict__ kflags, signers_view sv, uint32_t* __restrict__ match,
+    uint32_t* __restrict__ nlive, unsigned long long* __restrict__ matched) {
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t row = kNoKey;
+  if (s < cap) {
+    const uint32_t owner = slots[s];
+    if (owner != 0 && comb_key_hot(0, 0, kflags[s])) {
+      uint32_t w[8];
+      const uint32_t* key = pks + 8 * (i0 + (owner - 1));
+#pragma unroll
+      for (int t = 0; t < 8; ++t) w[t] = key[t];
+      row = signers_lookup(sv, w);
+    }
+    match[s] = row;
+  }
+  const uint64_t m = __ballot(row != kNoKey);
+  if (m && (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(m)) {
+    const uint32_t c = (uint32_t)__builtin_popcountll(m);
+    atomicAdd(nlive, c);
+    atomicAdd(matched, (unsigned long long)c);
+  }
+}
+
 // The slice's hot keys (comb_key_hot): one lane per slot; a hot slot takes the next dense index
 // while there are fewer than hot_cap (which slots win may differ from run to run, no status
 // does): hotidx[slot] = its index or kNoKey, hotrow[index] = the owner item's row in the slice.
 // *nhot may end above hot_cap; its readers clamp it. cstats[0] += hot keys taken.
+// With registered signers (match != nullptr, k_strict_signers_match's plane): one index space,
+// the nreg registry rows first, then the call-local tables. A matched slot gets its registry
+// row and takes no ticket (no table is built for it, whatever its use count); any other slot
+// that turns hot gets nreg + its ticket and adds one to *nlive.
 __global__ __launch_bounds__(256) void k_strict_comb_select(
     const uint32_t* __restrict__ slots, uint32_t cap, const uint32_t* __restrict__ kflags,
     const uint32_t* __restrict__ uses, uint32_t min_uses, uint32_t hot_cap,
     uint32_t* __restrict__ nhot, uint32_t* __restrict__ hotidx, uint32_t* __restrict__ hotrow,
-    unsigned long long* __restrict__ cstats) {
+    unsigned long long* __restrict__ cstats, const uint32_t* __restrict__ match, uint32_t nreg,
+    uint32_t* __restrict__ nlive) {
   const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= cap) return;
-  uint32_t h = kNoKey;
+  uint32_t h = match ? match[s] : kNoKey;
   const uint32_t owner = slots[s];
-  if (owner != 0 && comb_key_hot(uses[s], min_uses, kflags[s])) {
+  if (h == kNoKey && owner != 0 && hot_cap != 0 && comb_key_hot(uses[s], min_uses, kflags[s])) {
     const uint32_t t = atomicAdd(nhot, 1u);
     if (t < hot_cap) {
-      h = t;
+      h = nreg + t;
       hotrow[t] = owner - 1;
       atomicAdd(cstats, 1ull);
+      if (nlive) atomicAdd(nlive, 1u);
     }
   }
   hotidx[s] = h;
@@ -559,6 +596,31 @@ __global__ __launch_bounds__(256, NW_STRICT_WAVES) void k_verify_strict_pre(
 #ifndef NW_COMB_WAVES
 #define NW_COMB_WAVES 1
 #endif
+// The check of slice item i (global item gi) under the key whose comb tables are `tab` and whose
+// flag word is *okword (tab == nullptr: the item has no key here) and what it leaves behind:
+// status 0 for a pass, X' / Z' in the planes for a pending parity, the state word.
+__device__ __forceinline__ void strict_keyed_item(
+    const uint32_t* __restrict__ msgs, uint32_t msg_stride_words, const uint32_t* __restrict__ pks,
+    const uint32_t* __restrict__ sigs, uint64_t gi, uint64_t i, int32_t* __restrict__ status,
+    const ge_niels_pad* __restrict__ tab, const keyspec& ks, const uint32_t* __restrict__ okword,
+    const ge_niels_pad* __restrict__ bcomb, const vote_planes_t& vp) {
+  uint32_t st = kVoteFail;
+  if (tab) {
+    const strict_src_global src{pks + 8 * gi, sigs + 16 * gi,
+                                msgs + (uint64_t)msg_stride_words * gi};
+    fe X, Z;
+    st = keyed_vote_check(src, g_consts.sk, bcomb_wide{bcomb}, keytab_wide{tab, ks}, *okword, X, Z);
+    if (st >= kVotePending) {
+#pragma unroll
+      for (int k = 0; k < 10; ++k) {
+        vp.planes[(uint64_t)k * vp.S + i] = X.v[k];
+        vp.planes[(uint64_t)(10 + k) * vp.S + i] = Z.v[k];
+      }
+    }
+  }
+  if (st == kVotePass) status[gi] = NW_OK;
+  vp.state[i] = st;
+}
 template <bool HOT>
 __global__ __launch_bounds__(256, HOT ? NW_COMB_WAVES : NW_KEYED_WAVES) void k_strict_keyed(
     const uint32_t* __restrict__ msgs, uint32_t msg_stride_words, const uint32_t* __restrict__ pks,
@@ -580,23 +642,36 @@ __global__ __launch_bounds__(256, HOT ? NW_COMB_WAVES : NW_KEYED_WAVES) void k_s
     if (m && (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(m))
       atomicAdd(checked, (unsigned long long)__builtin_popcountll(m));
   }
-  uint32_t st = kVoteFail;
-  if (kk != kNoKey) {
-    const strict_src_global src{pks + 8 * gi, sigs + 16 * gi,
-                                msgs + (uint64_t)msg_stride_words * gi};
-    fe X, Z;
-    st = keyed_vote_check(src, g_consts.sk, bcomb_wide{bcomb},
-                          keytab_wide{keys.tabs + keys.ks.tab * (uint64_t)kk, keys.ks}, keys.ok[kk], X, Z);
-    if (st >= kVotePending) {
-#pragma unroll
-      for (int k = 0; k < 10; ++k) {
-        vp.planes[(uint64_t)k * vp.S + i] = X.v[k];
-        vp.planes[(uint64_t)(10 + k) * vp.S + i] = Z.v[k];
-      }
-    }
+  const bool has = kk != kNoKey;
+  strict_keyed_item(msgs, msg_stride_words, pks, sigs, gi, i, status,
+                    has ? keys.tabs + keys.ks.tab * (uint64_t)kk : nullptr, keys.ks,
+                    keys.ok + (has ? kk : 0u), bcomb, vp);
+}
+// The HOT instance over one index space (k_strict_comb_select with registered signers): index
+// kk < nreg is row kk of the registry's tables (rtabs, rok), any other one call-local table
+// kk - nreg of `keys`, valid below *nhot. A kernel of its own, so that k_strict_keyed<true>
+// keeps its code object; it counts nothing (k_strict_signers_count does, afterwards).
+// *nlive == 0: no hot key and no registered key in the slice, the triage takes all of it.
+__global__ __launch_bounds__(256, NW_COMB_WAVES) void k_strict_keyed_signers(
+    const uint32_t* __restrict__ msgs, uint32_t msg_stride_words, const uint32_t* __restrict__ pks,
+    const uint32_t* __restrict__ sigs, uint64_t i0, uint64_t ns, int32_t* __restrict__ status,
+    key_tables_t keys, const ge_niels_pad* __restrict__ bcomb, vote_planes_t vp,
+    const uint32_t* __restrict__ slotmap, const uint32_t* __restrict__ nhot,
+    const uint32_t* __restrict__ nlive, const ge_niels_pad* __restrict__ rtabs,
+    const uint32_t* __restrict__ rok, uint32_t nreg) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= ns || *nlive == 0) return;
+  uint32_t kk = keys.vote_key[i];
+  kk = kk != kNoSlot ? slotmap[kk] : kNoKey;
+  const bool reg = kk < nreg;
+  if (kk != kNoKey && !reg) {
+    kk -= nreg;
+    if (kk >= *nhot) kk = kNoKey;
   }
-  if (st == kVotePass) status[gi] = NW_OK;
-  vp.state[i] = st;
+  const bool has = kk != kNoKey;
+  strict_keyed_item(msgs, msg_stride_words, pks, sigs, i0 + i, i, status,
+                    has ? (reg ? rtabs : keys.tabs) + keys.ks.tab * (uint64_t)kk : nullptr, keys.ks,
+                    (reg ? rok : keys.ok) + (has ? kk : 0u), bcomb, vp);
 }
 
 // Parity of the pending items (Montgomery's trick per strided chunk, as k_votes_keyed_inv):
@@ -704,6 +779,46 @@ __global__ __launch_bounds__(256) void k_strict_todo_list(uint64_t ns,
       list[pos + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull))] =
           (uint32_t)(b0 + 256 * r + threadIdx.x);
     pos += (uint32_t)__builtin_popcountll(m);
+  }
+}
+
+// Diagnostics of a slice that ran k_strict_keyed_signers, after k_strict_keyed_inv (an item the
+// comb passed is any checked item whose state is not kVoteFail): ctr[c][lane] += the block's
+// items c = 0 checked, 1 checked under a registered key, 2 passed under one. A block takes
+// kTodoPer x 256 consecutive items and adds each of its sums with ONE atomic, spread over
+// kCombStatLanes addresses.
+__global__ __launch_bounds__(256) void k_strict_signers_count(
+    uint64_t ns, const uint32_t* __restrict__ keyslot, const uint32_t* __restrict__ slotmap,
+    const uint32_t* __restrict__ nhot, const uint32_t* __restrict__ nlive, uint32_t nreg,
+    const uint32_t* __restrict__ state, unsigned long long* __restrict__ ctr) {
+  __shared__ uint32_t s_sum[4][3];
+  if (*nlive == 0) return;
+  const uint64_t b0 = (uint64_t)blockIdx.x * (256 * kTodoPer);
+  uint32_t mine[3] = {0, 0, 0};
+#pragma unroll 1
+  for (uint32_t r = 0; r < kTodoPer; ++r) {
+    const uint64_t i = b0 + 256 * r + threadIdx.x;
+    bool any = false, reg = false, pass = false;
+    if (i < ns) {
+      const uint32_t slot = keyslot[i];
+      const uint32_t kk = slot != kNoSlot ? slotmap[slot] : kNoKey;
+      reg = kk < nreg;
+      any = reg || (kk != kNoKey && kk - nreg < *nhot);
+      pass = reg && state[i] != kVoteFail;
+    }
+    mine[0] += (uint32_t)__builtin_popcountll(__ballot(any));
+    mine[1] += (uint32_t)__builtin_popcountll(__ballot(reg));
+    mine[2] += (uint32_t)__builtin_popcountll(__ballot(pass));
+  }
+  if ((threadIdx.x & 63u) == 0)
+    for (int c = 0; c < 3; ++c) s_sum[threadIdx.x >> 6][c] = mine[c];
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const uint32_t c = threadIdx.x;
+    const uint32_t tot = s_sum[0][c] + s_sum[1][c] + s_sum[2][c] + s_sum[3][c];
+    if (tot)
+      atomicAdd(ctr + c * kCombStatLanes + (blockIdx.x & (kCombStatLanes - 1)),
+                (unsigned long long)tot);
   }
 }
 
@@ -1225,6 +1340,7 @@ strict_comb_plan_t strict_comb_plan(uint64_t slice, uint64_t key_slots) {
   if (const char* e = getenv("NW_STRICT_COMB"))
     if (e[0] == '0') return p;
   if (slice == 0 || key_slots == 0) return p;
+  p.on = true;
   if (const char* e = getenv("NW_STRICT_COMB_MIN")) {
     const unsigned long long v = strtoull(e, nullptr, 10);
     p.min = (uint32_t)std::min<unsigned long long>(std::max<unsigned long long>(v, 1), 1u << 30);
@@ -1234,20 +1350,26 @@ strict_comb_plan_t strict_comb_plan(uint64_t slice, uint64_t key_slots) {
   p.hot_cap = std::min<uint64_t>({keys, slice / p.min, 1ull << 20});
   return p;
 }
-// The path's allocation: a kCombBlockBytes block (nhot and the to-do count as words, then the
-// launch's counters: hot keys, items checked, items listed, 64 bits each from byte 8), the
-// to-do list (a word per item of the slice), per slot of the key set its uses and its hot
-// index, per hot key its owner's row and its flags, then the tables (key_tables_bytes).
+// The path's allocation: a kCombBlockBytes block (the slice's words: nhot, the to-do count and
+// nlive = hot keys + registered keys in the slice, kCombSliceBytes in all; then the launch's
+// counters, 64 bits each: hot keys, items checked, items listed from kCombStatsAt, registered
+// keys matched after them, and from kCombLanesAt 3 x kCombStatLanes of
+// k_strict_signers_count), the to-do list (a word per item of the slice), per slot of the key
+// set its uses, its hot index and its registry row, per hot key its owner's row and its flags,
+// then the tables (key_tables_bytes).
 namespace {
+constexpr uint64_t kCombSliceBytes = 16, kCombStatsAt = 16, kCombLanesAt = 1024;
+static_assert(kCombLanesAt + 8 * 3 * kCombStatLanes <= kCombBlockBytes, "the block's counters");
 struct comb_region_t {
-  uint64_t todo, uses, hotidx, hotrow, hok, tabs, bytes;
+  uint64_t todo, uses, hotidx, match, hotrow, hok, tabs, bytes;
 };
 comb_region_t comb_region_plan(uint64_t slice, uint64_t key_slots, uint64_t hot_cap) {
   comb_region_t r;
   r.todo = kCombBlockBytes;
   r.uses = r.todo + 4 * slice;
   r.hotidx = r.uses + 4 * key_slots;
-  r.hotrow = r.hotidx + 4 * key_slots;
+  r.match = r.hotidx + 4 * key_slots;
+  r.hotrow = r.match + 4 * key_slots;
   r.hok = r.hotrow + 4 * hot_cap;
   r.tabs = (r.hok + 4 * hot_cap + 255) & ~255ull;
   r.bytes = r.tabs + key_tables_bytes(hot_cap, keyspec_for(8));
@@ -1285,13 +1407,101 @@ hipError_t strict_comb_stats(uint64_t out[4], hipStream_t stream) {
   if (e != hipSuccess) return e;
   out[3] = rec.n;
   if (!rec.comb) return hipSuccess;
-  unsigned long long h[3];
-  e = hipMemcpy(h, rec.comb + 8, sizeof(h), hipMemcpyDeviceToHost);
+  std::vector<unsigned long long> h(kCombBlockBytes / 8);
+  e = hipMemcpy(h.data(), rec.comb, kCombBlockBytes, hipMemcpyDeviceToHost);
   if (e != hipSuccess) return e;
-  out[0] = h[0];
-  out[1] = h[1];
-  out[3] = h[2];
-  out[2] = rec.n - h[2];   // every item is either passed by the comb or listed
+  const unsigned long long* c = h.data() + kCombStatsAt / 8;
+  out[0] = c[0];
+  out[1] = c[1];   // k_strict_keyed<true>'s count, or k_strict_signers_count's lanes
+  for (uint32_t t = 0; t < kCombStatLanes; ++t) out[1] += h[kCombLanesAt / 8 + t];
+  out[3] = c[2];
+  out[2] = rec.n - c[2];   // every item is either passed by the comb or listed
+  return hipSuccess;
+}
+hipError_t strict_signers_stats(uint64_t out[3], hipStream_t stream) {
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  keyset_record_t rec;
+  {
+    std::lock_guard<std::mutex> g(g_keyset_m);
+    if (dev >= 0 && dev < 64) rec = g_keyset_last[dev];
+  }
+  out[0] = out[1] = out[2] = 0;
+  if (!rec.valid) return hipSuccess;
+  e = hipStreamSynchronize(stream);
+  if (e != hipSuccess || !rec.comb) return e;
+  std::vector<unsigned long long> h(kCombBlockBytes / 8);
+  e = hipMemcpy(h.data(), rec.comb, kCombBlockBytes, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return e;
+  out[0] = h[kCombStatsAt / 8 + 3];
+  for (uint32_t t = 0; t < kCombStatLanes; ++t) {
+    out[1] += h[kCombLanesAt / 8 + kCombStatLanes + t];
+    out[2] += h[kCombLanesAt / 8 + 2 * kCombStatLanes + t];
+  }
+  return hipSuccess;
+}
+
+// ---- the registered signers (nw_kernels.h strict_signers_t) ----
+uint64_t strict_signers_max() {
+  if (const char* e = getenv("NW_STRICT_SIGNERS_MAX")) return strtoull(e, nullptr, 10);
+  return 8192;
+}
+// Default 1: no measured size loses to the launch without the registry (DESIGN.md 5 "Round 10").
+uint64_t strict_signers_min_items() {
+  if (const char* e = getenv("NW_STRICT_SIGNERS_MIN_ITEMS")) return strtoull(e, nullptr, 10);
+  return 1;
+}
+void strict_signers_free(strict_signers_t* sg) {
+  if (sg->base) (void)hipFree(sg->base);
+  *sg = strict_signers_t{};
+}
+hipError_t strict_signers_build(const uint8_t* keys32, uint32_t n, strict_signers_t* out,
+                                hipStream_t stream) {
+  *out = strict_signers_t{};
+  if (n == 0) return hipSuccess;
+  // host: the keys as words, the hash table, the identity rows and their count
+  std::vector<uint32_t> keys(8 * (size_t)n), slots;
+  memcpy(keys.data(), keys32, 32 * (size_t)n);
+  const uint32_t cap = signers_hash_build(keys.data(), n, slots);
+  if (cap == 0) return hipErrorInvalidValue;
+  // one allocation: keys | slots | ok | rows | nlive, then the tables (256-byte aligned)
+  const keyspec ks8 = keyspec_for(8);
+  const uint64_t o_slots = 32ull * n, o_ok = o_slots + 4ull * cap, o_rows = o_ok + 4ull * n,
+                 o_live = o_rows + 4ull * n, o_tabs = (o_live + 4 + 255) & ~255ull;
+  void* base = nullptr;
+  hipError_t e = table_malloc(&base, o_tabs + key_tables_bytes(n, ks8));
+  if (e != hipSuccess) return e;
+  char* const b = static_cast<char*>(base);
+  std::vector<uint32_t> rows(n + 1);
+  for (uint32_t r = 0; r < n; ++r) rows[r] = r;
+  rows[n] = n;   // nlive, right behind the rows
+  e = hipMemcpyAsync(b, keys.data(), 32 * (size_t)n, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(b + o_slots, slots.data(), 4 * (size_t)cap, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(b + o_rows, rows.data(), 4 * (size_t)(n + 1), hipMemcpyHostToDevice, stream);
+  uint32_t* const ok = reinterpret_cast<uint32_t*>(b + o_ok);
+  ge_niels_pad* const tabs = reinterpret_cast<ge_niels_pad*>(b + o_tabs);
+  if (e == hipSuccess)
+    e = launch_key_tables_rows(reinterpret_cast<const uint32_t*>(b),
+                               reinterpret_cast<const uint32_t*>(b + o_rows),
+                               reinterpret_cast<const uint32_t*>(b + o_live), n, ks8, tabs, ok,
+                               stream);
+  // the uploads read this function's vectors: they must have left before it returns
+  const hipError_t e2 = hipStreamSynchronize(stream);
+  if (e == hipSuccess) e = e2;
+  if (e != hipSuccess) {
+    (void)hipFree(base);
+    return e;
+  }
+  out->base = base;
+  out->keys = reinterpret_cast<const uint32_t*>(b);
+  out->slots = reinterpret_cast<const uint32_t*>(b + o_slots);
+  out->ok = ok;
+  out->tabs = tabs;
+  out->n = n;
+  out->cap = cap;
   return hipSuccess;
 }
 hipError_t strict_keyset_stats(uint64_t out[3], hipStream_t stream) {
@@ -1337,7 +1547,10 @@ hipError_t launch_verify_strict(const uint32_t* msgs, uint32_t msg_stride_words,
   const char* kf = getenv("NW_STRICT_KEYED_FAST");
   // the comb check of the call's hot keys needs its allocation (Lease::strict_ws) and the B
   // comb; without either the launch runs without it
-  bool comb_on = !kt.vote_key && strict_triage_on() && wsp.comb && wsp.comb_keys && wsp.key_slots;
+  // (with registered signers the path runs even without room for call-local tables)
+  const strict_signers_t& sg = wsp.signers;
+  bool comb_on = !kt.vote_key && strict_triage_on() && wsp.comb && (wsp.comb_keys || sg.n) &&
+                 wsp.key_slots;
   if (comb_on && btab_for_current_device(1, &bcomb) != hipSuccess) {
     comb_on = false;
     bcomb = nullptr;
@@ -1375,15 +1588,22 @@ hipError_t launch_verify_strict(const uint32_t* msgs, uint32_t msg_stride_words,
     char* const cregion = comb_on ? static_cast<char*>(wsp.comb) : nullptr;
     uint32_t* const nhot = reinterpret_cast<uint32_t*>(cregion);
     uint32_t* const tcount = nhot + 1;
-    unsigned long long* const cstats = reinterpret_cast<unsigned long long*>(cregion + 8);
+    // with registered signers the skip test of the slice's comb kernels, the to-do list and the
+    // triage is "no hot key and no registered key": nlive; without them it is nhot, as before
+    const bool reg_on = comb_on && sg.n != 0;
+    uint32_t* const nlive = reg_on ? nhot + 2 : nhot;
+    unsigned long long* const cstats =
+        reinterpret_cast<unsigned long long*>(cregion + kCombStatsAt);
+    unsigned long long* const lanes = reinterpret_cast<unsigned long long*>(cregion + kCombLanesAt);
     uint32_t* const todo = reinterpret_cast<uint32_t*>(cregion + cg.todo);
     uint32_t* const uses = comb_on ? reinterpret_cast<uint32_t*>(cregion + cg.uses) : nullptr;
     uint32_t* const hotidx = reinterpret_cast<uint32_t*>(cregion + cg.hotidx);
+    uint32_t* const match = reinterpret_cast<uint32_t*>(cregion + cg.match);
     uint32_t* const hotrow = reinterpret_cast<uint32_t*>(cregion + cg.hotrow);
     uint32_t* const hok = reinterpret_cast<uint32_t*>(cregion + cg.hok);
     ge_niels_pad* const htabs = reinterpret_cast<ge_niels_pad*>(cregion + cg.tabs);
     if (comb_on) {
-      hipError_t e = hipMemsetAsync(cstats, 0, kCombBlockBytes - 8, stream);
+      hipError_t e = hipMemsetAsync(cstats, 0, kCombBlockBytes - kCombStatsAt, stream);
       if (e != hipSuccess) return e;
     }
     {
@@ -1405,7 +1625,7 @@ hipError_t launch_verify_strict(const uint32_t* msgs, uint32_t msg_stride_words,
         e = hipMemsetAsync(kslots, 0, 4 * (size_t)kcap, stream);
         if (e != hipSuccess) return e;
         if (comb_on) {
-          e = hipMemsetAsync(nhot, 0, 8, stream);   // nhot and the to-do count
+          e = hipMemsetAsync(nhot, 0, kCombSliceBytes, stream);   // nhot, the to-do count, nlive
           if (e == hipSuccess) e = hipMemsetAsync(uses, 0, 4 * (size_t)kcap, stream);
           if (e != hipSuccess) return e;
         }
@@ -1419,27 +1639,40 @@ hipError_t launch_verify_strict(const uint32_t* msgs, uint32_t msg_stride_words,
         // a pass is status 0 (k_strict_keyed, or k_strict_keyed_inv for the x parity); every
         // other item of the slice goes on the to-do list. X' / Z' and the state use the
         // region's planes 0-20, which the triage overwrites afterwards.
+        if (reg_on)
+          hipLaunchKernelGGL(k_strict_signers_match, dim3(grid_for(kcap, 256)), dim3(256), 0,
+                             stream, pks, i0, kslots, kcap, kflags,
+                             signers_view{sg.keys, sg.slots, sg.cap}, match, nlive, cstats + 3);
         hipLaunchKernelGGL(k_strict_comb_select, dim3(grid_for(kcap, 256)), dim3(256), 0, stream,
                            kslots, kcap, kflags, uses, wsp.comb_min, hot_cap, nhot, hotidx, hotrow,
-                           cstats);
+                           cstats, reg_on ? match : nullptr, reg_on ? sg.n : 0u,
+                           reg_on ? nlive : nullptr);
         hipError_t e2 = launch_key_tables_rows(pks + 8 * i0, hotrow, nhot, hot_cap, ks8, htabs, hok,
                                                stream);
         if (e2 != hipSuccess) return e2;
         const vote_planes_t vp{xs, xs + 20 * slice, slice, nullptr};
         const key_tables_t hk{htabs, hok, keyslot, ks8};
-        hipLaunchKernelGGL(k_strict_keyed<true>, dim3(grid_for(ns, 256)), dim3(256), 0, stream,
-                           msgs, msg_stride_words, pks, sigs, i0, ns, status, hk, bcomb, vp, 0,
-                           hotidx, nhot, cstats + 1);
+        if (reg_on)
+          hipLaunchKernelGGL(k_strict_keyed_signers, dim3(grid_for(ns, 256)), dim3(256), 0, stream,
+                             msgs, msg_stride_words, pks, sigs, i0, ns, status, hk, bcomb, vp,
+                             hotidx, nhot, nlive, sg.tabs, sg.ok, sg.n);
+        else
+          hipLaunchKernelGGL(k_strict_keyed<true>, dim3(grid_for(ns, 256)), dim3(256), 0, stream,
+                             msgs, msg_stride_words, pks, sigs, i0, ns, status, hk, bcomb, vp, 0,
+                             hotidx, nhot, cstats + 1);
         const uint64_t nchunks = std::min<uint64_t>(ns, 256ull * 4 * 2 * 64);
         hipLaunchKernelGGL(k_strict_keyed_inv, dim3(grid_for(nchunks, 256)), dim3(256), 0, stream,
-                           i0, ns, nchunks, status, vp, nhot);
+                           i0, ns, nchunks, status, vp, nlive);
+        if (reg_on)
+          hipLaunchKernelGGL(k_strict_signers_count, dim3(grid_for(ns, 256 * kTodoPer)), dim3(256),
+                             0, stream, ns, keyslot, hotidx, nhot, nlive, sg.n, vp.state, lanes);
         hipLaunchKernelGGL(k_strict_todo_list, dim3(grid_for(ns, 256 * kTodoPer)), dim3(256), 0,
-                           stream, ns, vp.state, todo, tcount, nhot);
+                           stream, ns, vp.state, todo, tcount, nlive);
       }
       hipLaunchKernelGGL(k_strict_triage, dim3(grid_for(ns, 256)), dim3(256), 0, stream, msgs,
                          msg_stride_words, pks, sigs, i0, ns, status, xs, slice, list, count,
                          keyslot, kflags, comb_on ? todo : nullptr, tcount,
-                         comb_on ? cstats + 2 : nullptr, nhot);
+                         comb_on ? cstats + 2 : nullptr, nlive);
       hipLaunchKernelGGL(k_verify_strict_pre,
                          dim3(std::min<uint64_t>(strict_grid(), grid_for(ns, 256))), dim3(256),
                          0, stream, msgs, msg_stride_words, pks, sigs, i0, list, count, xs,

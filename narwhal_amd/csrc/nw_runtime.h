@@ -121,6 +121,11 @@ class Lease {
   // (small jobs keep the wide tables) without host keys, without memory, or with
   // NW_SMALL_KEYW16=0.
   int small_tables(const uint32_t* dpks, size_t nkeys, const uint8_t* host_pks);
+  // Replaces the device's registered signers (nw::strict_signers_t) by the n distinct keys at
+  // keys32 (host memory): a writer, which waits for every strict launch queued on the device,
+  // frees the old tables and returns with the new ones built (n = 0: none). On an error
+  // (NW_E_OUT_OF_MEMORY, NW_E_INVALID_ARG for keys no hash table holds) the set is empty.
+  int signers_set(const uint8_t* keys32, size_t n);
   // Record the chain event on the stream and unlock (idempotent). 0 or NW_E_DEVICE.
   int release();
 

@@ -23,6 +23,8 @@
 #define NW_BWIN 24
 #endif
 
+#include <vector>
+
 #include "nw_ladder.hpp"
 
 namespace nw {
@@ -308,6 +310,63 @@ constexpr uint32_t kCombSample = 16;
 NW_HD bool comb_sampled(uint32_t j) { return ((j * 0x9e3779b1u) >> 28) == 0; }
 NW_HD bool comb_key_hot(uint32_t uses, uint32_t min_uses, uint32_t keyflags) {
   return uses >= min_uses && (keyflags & kKeyDecoded) != 0 && (keyflags & kKeySmall) == 0;
+}
+
+// ---- registered signers (DESIGN.md 5 "Round 10") ----
+// Keys a caller registers per device keep their 8-bit comb tables across calls, so their items
+// take the comb check whatever the call's size. The registry is `n` distinct keys (8 words
+// each, row r at keys[8 r..]) and an open-addressing table of `cap` (a power of two) words over
+// keyset_hash, slots[s] = row + 1 or 0, built on the host (signers_hash_build) so that every
+// key sits within kKeyProbes slots of its first one; the device only looks keys up. A key is
+// its 32 bytes: two encodings of one point are two keys, as in the call's key set.
+struct signers_view {
+  const uint32_t* keys;
+  const uint32_t* slots;
+  uint32_t cap;   // 0: nothing registered
+};
+// The registry row of the key w, or kNoKey (nw_kernels.h): at most kKeyProbes probes, an empty
+// slot ends the chain.
+NW_HD uint32_t signers_lookup(const signers_view& sv, const uint32_t w[8]) {
+  if (sv.cap == 0) return kNoKey;
+  uint32_t s = keyset_hash(w) & (sv.cap - 1);
+#pragma unroll 1
+  for (int p = 0; p < kKeyProbes; ++p, s = (s + 1) & (sv.cap - 1)) {
+    const uint32_t row = sv.slots[s];
+    if (row == 0) break;
+    const uint32_t* theirs = sv.keys + 8 * (uint64_t)(row - 1);
+    uint32_t d = 0;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) d |= w[t] ^ theirs[t];
+    if (d == 0) return row - 1;
+  }
+  return kNoKey;
+}
+// The table for n distinct keys: the smallest power of two >= max(2 n, 64) at which every key,
+// inserted in row order into the first empty slot of its chain, lands within kKeyProbes slots;
+// doubled until that holds (keys that share a first slot spread out as the mask takes more bits
+// of their hashes). More than kKeyProbes keys of one 32-bit hash never fit: past
+// kSignersSlotsMax slots the build gives up and returns 0. Returns cap, slots resized and filled.
+constexpr uint32_t kSignersSlotsMax = 1u << 26;
+inline uint32_t signers_hash_build(const uint32_t* keys, uint32_t n, std::vector<uint32_t>& slots) {
+  uint32_t cap = 64;
+  while (cap / 2 < n) cap <<= 1;
+  for (; cap <= kSignersSlotsMax; cap <<= 1) {
+    slots.assign(cap, 0u);
+    bool ok = true;
+    for (uint32_t r = 0; r < n && ok; ++r) {
+      uint32_t s = keyset_hash(keys + 8 * (uint64_t)r) & (cap - 1);
+      int p = 0;
+      while (p < kKeyProbes && slots[s] != 0) {
+        s = (s + 1) & (cap - 1);
+        ++p;
+      }
+      if (p == kKeyProbes) ok = false;
+      else slots[s] = r + 1;
+    }
+    if (ok) return cap;
+  }
+  slots.clear();
+  return 0;
 }
 
 // Inputs of one strict verification, fetched when needed (so nothing but the decompression

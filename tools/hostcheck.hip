@@ -540,6 +540,128 @@ int hc_verify_strict_comb_many(const uint8_t* pks, const uint8_t* sigs, const ui
   return 0;
 }
 
+// The registry of registered signers alone (nw_strict.hpp signers_hash_build / signers_lookup):
+// the host-built table for n distinct keys, then rows_out[i] = the registry row of probe i or
+// kNoKey. Returns the table's capacity, 0 when no table holds the keys, -1 when n > max_keys
+// (NW_STRICT_SIGNERS_MAX). slots_out (optional, cap words when the caller sized it from a first
+// call): the table itself.
+int64_t hc_signers_table(const uint8_t* keys, uint32_t n, uint64_t max_keys, const uint8_t* probes,
+                         uint32_t nprobes, uint32_t* rows_out, uint32_t* slots_out) {
+  if (n > max_keys) return -1;
+  std::vector<uint32_t> kw(8 * (size_t)n), slots;
+  if (n) memcpy(kw.data(), keys, 32 * (size_t)n);
+  const uint32_t cap = signers_hash_build(kw.data(), n, slots);
+  if (cap == 0) return 0;
+  const signers_view sv{kw.data(), slots.data(), n ? cap : 0u};
+  for (uint32_t i = 0; i < nprobes; ++i) {
+    uint32_t w[8];
+    load8(w, probes + 32 * (size_t)i);
+    rows_out[i] = signers_lookup(sv, w);
+  }
+  if (slots_out) memcpy(slots_out, slots.data(), 4 * (size_t)cap);
+  return (int64_t)cap;
+}
+
+// A slice the way launch_verify_strict runs it with registered signers (DESIGN.md 5
+// "Round 10"): hc_verify_strict_comb_many's sequence with the registry of the nreg distinct keys
+// at reg: the host-built hash table, the match of every slot of the slice's key set
+// (k_strict_signers_match), the selection over one index space (registry rows first, then the
+// call-local tables; a matched slot takes no ticket), the keyed check with either table, and
+// the leftovers through keyset_item. The path runs even when hot_cap is 0 (n < comb_min).
+// stats: as hc_verify_strict_comb_many (stats[0]: call-local tables only); sstats: registered
+// keys matched, items checked under them, items passed under them.
+int hc_verify_strict_signers_many(const uint8_t* pks, const uint8_t* sigs, const uint8_t* k32,
+                                  uint32_t n, uint64_t key_slots, int bw, uint32_t comb_min,
+                                  uint32_t comb_keys, const uint8_t* reg, uint32_t nreg,
+                                  int32_t* status_out, uint64_t stats[4], uint64_t sstats[3]) {
+  init();
+  if (n == 0) return 0;
+  // the registry: keys, hash table, flags and points (the device's tables, computed lazily)
+  std::vector<uint32_t> rkeys(8 * (size_t)nreg), rslots, rok(nreg);
+  if (nreg) memcpy(rkeys.data(), reg, 32 * (size_t)nreg);
+  const uint32_t rcap = signers_hash_build(rkeys.data(), nreg, rslots);
+  if (rcap == 0) return -3;
+  const signers_view sv{rkeys.data(), rslots.data(), nreg ? rcap : 0u};
+  std::vector<ge> regA(nreg);
+  for (uint32_t r = 0; r < nreg; ++r) {
+    const bool dec = ge_frombytes(regA[r], rkeys.data() + 8 * (size_t)r, K);
+    rok[r] = (dec ? kKeyDecoded : 0u) | (dec && ge_is_small_order(regA[r]) ? kKeySmall : 0u);
+  }
+  const uint64_t slice = ((uint64_t)n + 63) & ~63ull;
+  const uint32_t cap = (uint32_t)strict_keys_plan(key_slots, slice);
+  std::vector<uint32_t> keyslot(n), slots(cap), kflags(cap), uses(cap), hotidx(cap, kNoKey);
+  std::vector<ge_cached_pk> ktabs(8 * (size_t)cap);
+  std::vector<uint32_t> pkw(8 * (size_t)n);
+  memcpy(pkw.data(), pks, 32 * (size_t)n);
+  uint32_t nkeys = 0;
+  for (uint32_t j = 0; j < n; ++j) {
+    keyslot[j] = cap ? keyset_probe(slots.data(), cap, cap / 2, &nkeys, pkw.data(), 0, j,
+                                    plain_atomics{})
+                     : kNoSlot;
+    if (keyslot[j] != kNoSlot && comb_sampled(j)) uses[keyslot[j]] += kCombSample;
+  }
+  for (uint32_t s = 0; s < cap; ++s)
+    keyset_build(slots.data(), s, pkw.data(), 0, SK, kflags.data(), ktabs.data());
+  const bool on = comb_min != 0 && cap != 0;
+  const uint64_t hot_cap = on ? std::min<uint64_t>(comb_keys, slice / comb_min) : 0;
+  std::vector<ge> hotA;
+  uint64_t matched = 0;
+  for (uint32_t s = 0; on && s < cap; ++s) {
+    if (slots[s] == 0) continue;
+    const uint32_t* key = pkw.data() + 8 * (size_t)(slots[s] - 1);
+    uint32_t row = kNoKey;
+    if (nreg && comb_key_hot(0, 0, kflags[s])) row = signers_lookup(sv, key);
+    if (row != kNoKey) {
+      hotidx[s] = row;
+      ++matched;
+    } else if (hotA.size() < hot_cap && comb_key_hot(uses[s], comb_min, kflags[s])) {
+      ge A;
+      if (!ge_frombytes(A, key, K)) return -2;
+      hotidx[s] = nreg + (uint32_t)hotA.size();
+      hotA.push_back(A);
+    }
+  }
+  uint64_t checked = 0, passed = 0, rchecked = 0, rpassed = 0;
+  const keyspec ks8 = keyspec_for(8);
+  for (uint32_t j = 0; j < n; ++j) {
+    uint32_t Aw[8], Rw[8], Sw[8], kw[8];
+    load8(Aw, pks + 32 * (size_t)j); load8(Rw, sigs + 64 * (size_t)j);
+    load8(Sw, sigs + 64 * (size_t)j + 32); load8(kw, k32 + 32 * (size_t)j);
+    const uint32_t h = keyslot[j] != kNoSlot ? hotidx[keyslot[j]] : kNoKey;
+    if (h != kNoKey) {
+      const bool isreg = h < nreg;
+      ++checked;
+      rchecked += isreg;
+      const strict_src_arrays src{Aw, Rw, Sw, kw};
+      fe X, Z;
+      uint32_t st = keyed_vote_check(src, SK, bcomb_lazy{BT, &SK.k.d2},
+                                     keytab_lazy{isreg ? &regA[h] : &hotA[h - nreg], &SK.k.d2, ks8},
+                                     isreg ? rok[h] : kKeyDecoded, X, Z);
+      if (st >= kVotePending) {
+        fe zi, x;
+        fe_invert(zi, Z);
+        fe_mul(x, X, zi);
+        st = fe_isnegative(x) == (st & 1) ? kVotePass : kVoteFail;
+      }
+      if (st == kVotePass) {
+        status_out[j] = NW_OK;
+        ++passed;
+        rpassed += isreg;
+        continue;
+      }
+    }
+    src_arrays_keys src{};
+    src.a = Aw; src.r = Rw; src.s = Sw; src.k = kw;
+    src.ktabs = ktabs.data();
+    status_out[j] = bw == -24
+        ? keyset_item<24>(src, btab_lazy_entry{{BT, &SK.k.d2}, {}}, keyslot[j], kflags.data())
+        : keyset_item<16>(src, btab_wide{BTW, BTW_N}, keyslot[j], kflags.data());
+  }
+  if (stats) { stats[0] = hotA.size(); stats[1] = checked; stats[2] = passed; stats[3] = n - passed; }
+  if (sstats) { sstats[0] = matched; sstats[1] = rchecked; sstats[2] = rpassed; }
+  return 0;
+}
+
 // k's digits at comb width w (key_recode / key_digit): digits[t], t < ntab; returns ntab.
 int hc_key_digits(const uint8_t k32[32], int w, int32_t digits[32]) {
   const keyspec ks = keyspec_for((uint32_t)w);
@@ -570,7 +692,9 @@ void hc_wide_btab_entry(int h, uint32_t j, uint32_t out[30]) {
 #ifdef KEYSET_SAN_MAIN
 // make keysetsan && tools/keyset_san: the key set's sizing and region planning
 // (nw_kernels.h strict_keys_plan / strict_region_plan) and the probe -> build -> triage ->
-// ladder sequence over that region, as a stand-alone program under AddressSanitizer / UBSan.
+// ladder sequence over that region, then the registered signers' hash table (build, lookup,
+// limit) and one slice through a registry, as a stand-alone program under AddressSanitizer /
+// UBSan.
 #include <stdio.h>
 #include <vector>
 static int san_fail(const char* what, uint64_t a, uint64_t b) {
@@ -622,6 +746,50 @@ int main() {
         return san_fail("run (on)", n, slots);
       if (on != off) return san_fail("statuses differ", n, slots);
       if (st[1] + st[2] != n || st[0] > 32768 || st[1] == 0) return san_fail("stats (on)", st[0], st[1]);
+    }
+  }
+  // registered signers: the hash table for a few hundred keys (every one found, strangers
+  // not), then one slice through the registry: some keys registered, below and above the
+  // call-local threshold, against the same slice without a registry
+  {
+    const uint32_t nk = 300, n = 300;
+    std::vector<uint8_t> keys(32 * nk), strangers(32 * 64);
+    for (auto& b : keys) b = rnd();
+    for (auto& b : strangers) b = rnd();
+    std::vector<uint32_t> rows(nk);
+    const int64_t cap = hc_signers_table(keys.data(), nk, 8192, keys.data(), nk, rows.data(), nullptr);
+    if (cap < 2 * nk || (cap & (cap - 1))) return san_fail("signers: capacity", (uint64_t)cap, nk);
+    for (uint32_t r = 0; r < nk; ++r)
+      if (rows[r] != r) return san_fail("signers: lookup", r, rows[r]);
+    if (hc_signers_table(keys.data(), nk, 8192, strangers.data(), 64, rows.data(), nullptr) != cap)
+      return san_fail("signers: capacity (again)", 0, 0);
+    for (uint32_t r = 0; r < 64; ++r)
+      if (rows[r] != kNoKey) return san_fail("signers: stranger found", r, rows[r]);
+    if (hc_signers_table(keys.data(), 0, 8192, strangers.data(), 64, rows.data(), nullptr) <= 0)
+      return san_fail("signers: empty", 0, 0);
+    if (hc_signers_table(keys.data(), nk, nk - 1, nullptr, 0, nullptr, nullptr) != -1)
+      return san_fail("signers: limit", 0, 0);
+    std::vector<uint8_t> pks(32 * n), sigs(64 * n), ks(32 * n);
+    for (uint32_t j = 0; j < n; ++j) {
+      memcpy(&pks[32 * j], &keys[32 * (j % 5)], 32);
+      for (int t = 0; t < 64; ++t) sigs[64 * j + t] = rnd();
+      sigs[64 * j + 63] &= 0x0f;
+      for (int t = 0; t < 32; ++t) ks[32 * j + t] = rnd();
+      ks[32 * j + 31] &= 0x0f;
+    }
+    std::vector<int32_t> off(n), on(n);
+    uint64_t st[4], ss[3];
+    if (hc_verify_strict_signers_many(pks.data(), sigs.data(), ks.data(), n, 65536, -16, 256, 8192,
+                                      nullptr, 0, off.data(), st, ss))
+      return san_fail("signers: run (none)", 0, 0);
+    if (ss[0] || ss[1] || ss[2] || st[1]) return san_fail("signers: stats (none)", ss[0], st[1]);
+    for (uint32_t cmin : {256u, 32u}) {
+      if (hc_verify_strict_signers_many(pks.data(), sigs.data(), ks.data(), n, 65536, -16, cmin, 8192,
+                                        keys.data(), 3, on.data(), st, ss))
+        return san_fail("signers: run", cmin, 0);
+      if (on != off) return san_fail("signers: statuses differ", cmin, 0);
+      if (ss[0] > 3 || ss[2] > ss[1] || ss[1] > st[1] || st[2] + st[3] != n)
+        return san_fail("signers: stats", ss[0], ss[1]);
     }
   }
   printf("keyset_san ok\n");

@@ -21,12 +21,19 @@ slots of the call's key set, 0 = off; NW_TRIAGE_SLICE), e.g.
     LIB LIB@NW_STRICT_KEYS=0
 --keys K: the corpus's signers (bench.py's config 4 has 4,096); K = 0: every item has a key
 of its own (then all items are valid: keys and signatures made on the device, no edits).
+--signers: every LIB becomes two variants of the same library and corpus, LIB#registered (the
+corpus's K signers registered with nw_strict_signers_set before the round's launches) and
+LIB#cleared (the registry emptied), alternating round by round (--registered-only: the first
+alone, for a kernel trace).
+--host-calls C: time C blocking host-buffer calls per round instead of device launches
+(nw_signature_verify for --items 1, else nw_verify_strict_many), wall clock per call.
 """
 import argparse
 import ctypes
 import json
 import os
 import sys
+import time
 
 import numpy as np
 import torch
@@ -71,6 +78,13 @@ def load(path):
     L.nw_last_error.restype = ctypes.c_char_p
     L.nw_dev_verify_strict_many.argtypes = [P, S, P, P, S, P, P, P]
     L.nw_dev_verify_strict_many.restype = I
+    L.nw_verify_strict_many.argtypes = [P, S, P, P, S, P, P]
+    L.nw_verify_strict_many.restype = I
+    L.nw_signature_verify.argtypes = [P, P, P]
+    L.nw_signature_verify.restype = I
+    if hasattr(L, "nw_strict_signers_set"):
+        L.nw_strict_signers_set.argtypes = [P, S]
+        L.nw_strict_signers_set.restype = I
     assert L.nw_init() > 0, L.nw_last_error()
     assert L.nw_set_device(0) == 0
     return L
@@ -86,8 +100,17 @@ def main():
                     help="tile only the corpus's valid items (no early-decided statuses)")
     ap.add_argument("--keys", type=int, default=4096,
                     help="signers of the corpus; 0 = a key per item (all valid)")
+    ap.add_argument("--signers", action="store_true",
+                    help="each LIB as LIB#registered and LIB#cleared (nw_strict_signers_set)")
+    ap.add_argument("--registered-only", action="store_true",
+                    help="with --signers: the registered variant alone (for a kernel trace)")
+    ap.add_argument("--host-calls", type=int, default=0,
+                    help="time this many blocking host-buffer calls per round, not launches")
     ap.add_argument("libs", nargs="+")
     a = ap.parse_args()
+    if a.signers:
+        tags = ("#registered",) if a.registered_only else ("#registered", "#cleared")
+        a.libs = [x + tag for x in a.libs for tag in tags]
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     ts = torch.cuda.Stream(device=dev)
@@ -110,7 +133,13 @@ def main():
         m, p, s = (t.index_select(0, idx).contiguous() for t in (m_u, p_u, s_u))
         del idx
         exp = np.resize(valid, n)
-    variants = [split_variant(x) for x in a.libs]
+    variants = [split_variant(x.partition("#")[0]) for x in a.libs]
+    signers = None
+    if a.signers:   # the K most used keys of the corpus
+        keys, counts = np.unique(p.cpu().numpy(), axis=0, return_counts=True)
+        signers = np.ascontiguousarray(keys[np.argsort(-counts, kind="stable")[:max(a.keys, 1)]])
+    hm, hp, hs = ((t.cpu().numpy() for t in (m, p, s)) if a.host_calls else (None,) * 3)
+    hst, hbm = np.zeros(n, np.int32), np.zeros((n + 7) // 8, np.uint8)
     loaded = {}
     for path, _ in variants:
         if path not in loaded:
@@ -123,11 +152,25 @@ def main():
     ok = {}
     for rep in range(a.reps):
         for name, L, (_, env) in zip(a.libs, libs, variants):
+            if a.signers:
+                reg = signers if name.endswith("#registered") else signers[:0]
+                rc = L.nw_strict_signers_set(reg.ctypes.data if len(reg) else None, len(reg))
+                assert rc == 0, L.nw_last_error()
+
             def launch():
                 old = {k: os.environ.get(k) for k in env}
                 os.environ.update(env)
                 try:
-                    rc = L.nw_dev_verify_strict_many(P(m), 32, P(p), P(s), n, P(st), P(bm), stream)
+                    if not a.host_calls:
+                        rc = L.nw_dev_verify_strict_many(P(m), 32, P(p), P(s), n, P(st), P(bm), stream)
+                    elif n == 1:
+                        rc = L.nw_signature_verify(hs.ctypes.data, hm.ctypes.data, hp.ctypes.data)
+                        hst[0] = rc
+                        rc = min(rc, 0)
+                    else:
+                        rc = L.nw_verify_strict_many(hm.ctypes.data, 32, hp.ctypes.data,
+                                                     hs.ctypes.data, n, hst.ctypes.data,
+                                                     hbm.ctypes.data)
                 finally:
                     for k, v in old.items():
                         if v is None:
@@ -138,7 +181,13 @@ def main():
             launch()
             torch.cuda.synchronize()
             if rep == 0:
-                ok[name] = bool(np.array_equal(st.cpu().numpy() == 0, exp))
+                ok[name] = bool(np.array_equal((hst if a.host_calls else st.cpu().numpy()) == 0, exp))
+            if a.host_calls:
+                for _ in range(a.host_calls):
+                    t0 = time.perf_counter()
+                    launch()
+                    times[name].append((time.perf_counter() - t0) * 1e3)
+                continue
             evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                    for _ in range(a.steps)]
             for e0, e1 in evs:
@@ -147,11 +196,15 @@ def main():
                 e1.record()
             torch.cuda.synchronize()
             times[name] += [e0.elapsed_time(e1) for e0, e1 in evs]
+    per = a.host_calls or a.steps
+    if a.signers:
+        for L in loaded.values():
+            L.nw_strict_signers_set(None, 0)
     for name in a.libs:
         ms = float(np.median(times[name]))
         print(json.dumps({"lib": name, "median_ms": ms, "verifies_per_s": n / ms * 1e3,
                           "min_ms": float(np.min(times[name])),
-                          "rep_medians_ms": [float(np.median(times[name][r * a.steps:(r + 1) * a.steps]))
+                          "rep_medians_ms": [float(np.median(times[name][r * per:(r + 1) * per]))
                                              for r in range(a.reps)],
                           "parity": ok[name]}), flush=True)
 
