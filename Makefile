@@ -1,6 +1,7 @@
 # Builds the MI355X engine (narwhal_amd/libnarwhal_amd.so, gfx950 only), the CPU oracle
 # (test infrastructure) and the host check libraries of the kernels' arithmetic, of the wire
-# decoder and of the message jobs' staging layout (test infrastructure).
+# decoder and of the message jobs' staging layout, and the gfx950 harness of the arithmetic on
+# raw limbs (test infrastructure).
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Iinclude -Inarwhal_amd/csrc -Wall -Wno-unused-function
@@ -9,7 +10,7 @@ HDRS := $(wildcard $(CSRC)/*.hpp) $(CSRC)/nw_kernels.h $(CSRC)/nw_runtime.h $(CS
 LIB := narwhal_amd/libnarwhal_amd.so
 BUILD := build
 
-all: $(LIB) oracle hostcheck wirecheck stagecheck loadgen
+all: $(LIB) oracle hostcheck lpcheck wirecheck stagecheck loadgen
 
 $(BUILD)/nw_kernels.o: $(CSRC)/nw_kernels.hip $(HDRS)
 	@mkdir -p $(BUILD)
@@ -58,8 +59,14 @@ oracle:
 	$(MAKE) -s -C oracle
 
 hostcheck: tools/libnw_hostcheck.so
-tools/libnw_hostcheck.so: tools/hostcheck.hip $(HDRS)
+tools/libnw_hostcheck.so: tools/hostcheck.hip tools/limb_ops.hpp $(HDRS)
 	$(HIPCC) --cuda-host-only -O2 -std=c++17 -fPIC -shared -Iinclude $< -o $@
+
+# the per-lane field / point routines and the limb-parallel ones (nw_lp.hpp) as gfx950 kernels
+# over raw limbs (tests/test_gpu_field_limbs.py); a library of its own, not linked into $(LIB)
+lpcheck: tools/libnw_lpcheck.so
+tools/libnw_lpcheck.so: tools/lpcheck.hip tools/limb_ops.hpp $(HDRS)
+	$(HIPCC) -O3 -std=c++17 -fPIC -shared --offload-arch=$(ARCH) -Iinclude -Wall -Wno-unused-function $< -o $@
 
 # the device wire decoder (nw_wiredec.hpp) and the host placement (nw_wireplace.hpp) compiled for
 # the CPU (tests/test_wire_device_cpu.py, test_wire_canon_cpu.py, test_wire_place_cpu.py)
@@ -111,7 +118,7 @@ tools/ubench_valu: tools/ubench_valu.hip
 	$(HIPCC) --offload-arch=$(ARCH) -O3 $< -o $@
 
 clean:
-	rm -rf $(BUILD) $(LIB) tools/libnw_hostcheck.so tools/libnw_wirecheck.so tools/libnw_stagecheck.so tools/libnw_loadgen.so tools/service_stress tools/service_stress_tsan tools/wire_canon_san tools/stage_san tools/keyset_san
+	rm -rf $(BUILD) $(LIB) tools/libnw_hostcheck.so tools/libnw_lpcheck.so tools/libnw_wirecheck.so tools/libnw_stagecheck.so tools/libnw_loadgen.so tools/service_stress tools/service_stress_tsan tools/wire_canon_san tools/stage_san tools/keyset_san
 	$(MAKE) -s -C oracle clean
 
-.PHONY: all oracle hostcheck wirecheck stagecheck wiresan stagesan keysetsan loadgen stress ubench clean
+.PHONY: all oracle hostcheck lpcheck wirecheck stagecheck wiresan stagesan keysetsan loadgen stress ubench clean

@@ -5,14 +5,21 @@
 // on gfx950 v_mad_u64_u32 issues at the same half rate as v_add_co/v_addc/v_alignbit, so a
 // radix-2^32 schoolbook product (64 MACs + ~60 carry ops) costs about as much as this
 // radix's 100 MACs, and here every column accumulates in a 64-bit register with no carry
-// instructions at all (column sums stay < 2^63 for the input bounds below).
+// instructions at all (column sums with their carry-in stay < 2^64 for the input bounds
+// below).
 //
 // Bounds (per limb, even/odd):  T ("tight", every mul/sq/sub output) <= 2^26 / 2^25 (+2^18)
 //                               L ("loose", sum of two T)            <= 2^27 / 2^26
-// fe_mul / fe_sq accept inputs up to 1.5 * L: every column stays below 2^63.
-// fe_sub(a, b) = a + 4p - b, carried to T; valid for b up to 2^28 per limb.
+// fe_mul accepts a second operand up to P15 = 1.5 * L (scaled by 19 in 32 bits) and a first
+// one up to S_L = L + 4p (an uncarried difference, fe_sub_nc); fe_sq accepts L. Over every
+// operand pair the point formulas produce, the largest column with its carry-in is 2^63.13
+// (S_L x P15), below 2^64; tests/test_field_bounds.py is the model, and
+// tests/test_field_limbs_cpu.py runs this code on operands at exactly those bounds.
+// fe_sub(a, b) = a + 4p - b, carried to T; valid while no limb of b exceeds that limb of 4p
+// (2^28 - 4 even, 2^27 - 4 odd; limb 0: 2^28 - 76), the difference being formed per limb in
+// unsigned 32 bits, and a up to P15.
 //
-// Compiles for host and device (NW_HD) so tools/host_selftest can check the exact same
+// Compiles for host and device (NW_HD) so tools/hostcheck.hip can check the exact same
 // code on the CPU; the product library only runs it on the GPU.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -121,8 +128,9 @@ NW_HD void fe_neg_nc(fe& h, const fe& f) { fe z; fe_0(z); fe_sub_nc(h, z, f); }
 // two interleaved chains (independent v_mad_u64_u32 streams, so no dependent-issue wait
 // states); inside a chain each column's carry is the initial accumulator of the next one,
 // so no separate 64-bit add per step. fe_join finishes: a = column 4 (its carry goes into
-// limb 5), b = column 9 (its carry wraps to limb 0 times 19). Every column stays < 2^63
-// (input bounds above), so carries are < 2^39 and limbs land in T.
+// limb 5), b = column 9 (its carry wraps to limb 0 times 19). Every column stays < 2^64
+// (input bounds above), so carries are < 2^39 and limbs land in T; limb 1 may be left at
+// 2^25 + 2^17.3 and limb 6 at 2^26 + 2^13 (not re-split), which T includes.
 NW_HD void fe_join(fe& h, uint64_t a, uint64_t b) {
   h.v[4] = (uint32_t)a & M26;
   h.v[9] = (uint32_t)b & M25;

@@ -21,6 +21,16 @@
 // Operand discipline is nw_point.hpp's (same products, same first/second operand roles:
 // the second operand is the one scaled by 19, the first by 2); lp_carry64 leaves limbs in
 // the T_LP bound, for which tests/test_field_bounds.py checks every operand pair.
+//
+// Lanes 10..15 ("dead" lanes). Every routine that multiplies or carries (lp_mul, lp_carry32,
+// lp_sub, lp_dbl, lp_add, lp_to_cached, lp_sqn, lp_pow22523) IGNORES what its operands' dead
+// lanes hold and returns 0 there; lp_is_identity reads live lanes only; lp_identity,
+// lp_cached_component and lp_niels_component return 0 there. The lane-wise routines
+// (lp_rows_of, lp_sel, lp_sub_nc, and the plain additions between them) pass dead lanes
+// through like any other lane: 0 in, 0 out, and since each feeds a multiply or a carry before
+// anything is stored, a point held between calls always has 0 in its dead lanes. Stores write
+// live lanes only. tests/test_gpu_field_limbs.py checks all of this per routine, on raw limbs
+// at the bounds (tools/lpcheck.hip).
 #pragma once
 #include "nw_point.hpp"
 
@@ -231,6 +241,33 @@ __device__ __forceinline__ bool lp_is_identity(const lp_ctx& c, uint32_t v, uint
     Z.v[i] = s_tmp[20 + i];
   }
   return fe_iszero(X) && fe_eq(Y, Z);
+}
+
+// z^((p-5)/8) for the four field elements of a wave's rows (nw_lp.hpp: row r = one element,
+// limb k in lane 16 r + k), the addition chain of fe_pow22523: 252 squarings and 11
+// multiplications, each a limb-parallel product (a dependent chain of ~75 VALU instructions
+// instead of a 10-limb serial product on one lane). Every operand is a limb-parallel
+// product's output (the T_LP bound, tests/test_field_bounds.py) or the canonical input.
+__device__ __forceinline__ uint32_t lp_sqn(const lp_ctx& c, uint32_t x, int n) {
+#pragma unroll 1
+  for (int i = 0; i < n; ++i) x = lp_mul(c, x, x);
+  return x;
+}
+__device__ __forceinline__ uint32_t lp_pow22523(const lp_ctx& c, uint32_t z) {
+  const uint32_t z2 = lp_mul(c, z, z);                          // 2
+  uint32_t t = lp_sqn(c, z2, 2);                                // 8
+  const uint32_t z9 = lp_mul(c, t, z);                          // 9
+  const uint32_t z11 = lp_mul(c, z9, z2);                       // 11
+  t = lp_mul(c, z11, z11);                                      // 22
+  const uint32_t z5 = lp_mul(c, t, z9);                         // 2^5 - 1
+  const uint32_t z10 = lp_mul(c, lp_sqn(c, z5, 5), z5);         // 2^10 - 1
+  const uint32_t z20 = lp_mul(c, lp_sqn(c, z10, 10), z10);      // 2^20 - 1
+  t = lp_mul(c, lp_sqn(c, z20, 20), z20);                       // 2^40 - 1
+  const uint32_t z50 = lp_mul(c, lp_sqn(c, t, 10), z10);        // 2^50 - 1
+  const uint32_t z100 = lp_mul(c, lp_sqn(c, z50, 50), z50);     // 2^100 - 1
+  t = lp_mul(c, lp_sqn(c, z100, 100), z100);                    // 2^200 - 1
+  t = lp_mul(c, lp_sqn(c, t, 50), z50);                         // 2^250 - 1
+  return lp_mul(c, lp_sqn(c, t, 2), z);                         // 2^252 - 3
 }
 
 }  // namespace nw

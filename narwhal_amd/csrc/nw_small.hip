@@ -97,33 +97,6 @@ __device__ __forceinline__ ge shfl_down_ge(const ge& p, int off) {
 
 __device__ __forceinline__ void release_vm() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
-// z^((p-5)/8) for the four field elements of a wave's rows (nw_lp.hpp: row r = one element,
-// limb k in lane 16 r + k), the addition chain of fe_pow22523: 252 squarings and 11
-// multiplications, each a limb-parallel product (a dependent chain of ~75 VALU instructions
-// instead of a 10-limb serial product on one lane). Every operand is a limb-parallel
-// product's output (the T_LP bound, tests/test_field_bounds.py) or the canonical input.
-__device__ __forceinline__ uint32_t lp_sqn(const lp_ctx& c, uint32_t x, int n) {
-#pragma unroll 1
-  for (int i = 0; i < n; ++i) x = lp_mul(c, x, x);
-  return x;
-}
-__device__ __forceinline__ uint32_t lp_pow22523(const lp_ctx& c, uint32_t z) {
-  const uint32_t z2 = lp_mul(c, z, z);                          // 2
-  uint32_t t = lp_sqn(c, z2, 2);                                // 8
-  const uint32_t z9 = lp_mul(c, t, z);                          // 9
-  const uint32_t z11 = lp_mul(c, z9, z2);                       // 11
-  t = lp_mul(c, z11, z11);                                      // 22
-  const uint32_t z5 = lp_mul(c, t, z9);                         // 2^5 - 1
-  const uint32_t z10 = lp_mul(c, lp_sqn(c, z5, 5), z5);         // 2^10 - 1
-  const uint32_t z20 = lp_mul(c, lp_sqn(c, z10, 10), z10);      // 2^20 - 1
-  t = lp_mul(c, lp_sqn(c, z20, 20), z20);                       // 2^40 - 1
-  const uint32_t z50 = lp_mul(c, lp_sqn(c, t, 10), z10);        // 2^50 - 1
-  const uint32_t z100 = lp_mul(c, lp_sqn(c, z50, 50), z50);     // 2^100 - 1
-  t = lp_mul(c, lp_sqn(c, z100, 100), z100);                    // 2^200 - 1
-  t = lp_mul(c, lp_sqn(c, t, 50), z50);                         // 2^250 - 1
-  return lp_mul(c, lp_sqn(c, t, 2), z);                         // 2^252 - 3
-}
-
 // Diagnostic phase stamps (NW_SMALL_STAMPS, small_job_t::stamps): s_memrealtime (100 MHz)
 // per workgroup at the phase boundaries below, written by one lane of the wave that ends
 // the phase; no output depends on them.

@@ -94,15 +94,18 @@ def test_uncarried_operand_needs_first_slot():
 T_LP = [2**26 + 2**18.3 if i == 0 else 2**25 + 2**17.3 if i == 1 else
         (2**26 if i % 2 == 0 else 2**25) + 2**14 for i in range(10)]
 T_LP = [int(x) + 1 for x in T_LP]
+# the same shapes over T_LP, and every (first, second) operand pair of the limb-parallel code
+# (module level so that the limb-level tests, tests/limb_cases.py, feed lp_mul exactly these)
+L_ = [2 * x for x in T_LP]
+P15_ = [a + b for a, b in zip(T_LP, L_)]
+S_T_ = [a + b for a, b in zip(T_LP, P4)]
+S_L_ = [a + b for a, b in zip(L_, P4)]
+LP_PAIRS = [(S_T_, T_LP), (S_T_, L_), (T_LP, P15_), (P15_, L_), (S_L_, P15_), (S_L_, L_),
+            (P15_, T_LP), (T_LP, T_LP), (T_LP, T_LP), (L_, L_)]
 
 
 def test_limb_parallel_bounds():
-    L_ = [2 * x for x in T_LP]
-    P15_ = [a + b for a, b in zip(T_LP, L_)]
-    S_T_ = [a + b for a, b in zip(T_LP, P4)]
-    S_L_ = [a + b for a, b in zip(L_, P4)]
-    pairs = [(S_T_, T_LP), (S_T_, L_), (T_LP, P15_), (P15_, L_), (S_L_, P15_), (S_L_, L_),
-             (P15_, T_LP), (T_LP, T_LP), (T_LP, T_LP), (L_, L_)]
+    pairs = LP_PAIRS
     for F, G in pairs:
         c = colmax(F, G)
         assert c < 2**64

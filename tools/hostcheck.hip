@@ -7,6 +7,7 @@
 #include <vector>
 #include "../narwhal_amd/csrc/nw_consts.hpp"
 #include "../narwhal_amd/csrc/nw_ladder.hpp"
+#include "limb_ops.hpp"
 
 using namespace nw;
 
@@ -685,6 +686,26 @@ uint32_t hc_keyset_hash(const uint8_t pk[32]) {
 void hc_wide_btab_entry(int h, uint32_t j, uint32_t out[30]) {
   init();
   memcpy(out, &BTW[(h ? BTW_N : 0u) + j].n, 120);
+}
+
+// The field (hc_fe_ops) and point (hc_ge_ops) routines on raw limbs (tools/limb_ops.hpp: the
+// operation codes and the 40-word operand layout), n cases of one operation per call. No
+// fe_frombytes in front, so the limbs arrive exactly as given: at their bounds, uncarried,
+// non-canonical (tests/test_field_limbs_cpu.py). Returns 0, or -1 for an operation code the
+// entry does not serve.
+int hc_fe_ops(int op, uint32_t n, const uint32_t* A, const uint32_t* B, const int32_t* k,
+              uint32_t* out) {
+  if (op < 0 || op >= OP_GE_DBL) return -1;
+  for (uint32_t i = 0; i < n; ++i)
+    if (!limb_op(op, A + 40 * (size_t)i, B + 40 * (size_t)i, k[i], out + 40 * (size_t)i)) return -1;
+  return 0;
+}
+int hc_ge_ops(int op, uint32_t n, const uint32_t* A, const uint32_t* B, const int32_t* k,
+              uint32_t* out) {
+  if (op < OP_GE_DBL) return -1;
+  for (uint32_t i = 0; i < n; ++i)
+    if (!limb_op(op, A + 40 * (size_t)i, B + 40 * (size_t)i, k[i], out + 40 * (size_t)i)) return -1;
+  return 0;
 }
 
 }
