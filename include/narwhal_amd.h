@@ -222,6 +222,13 @@ int nw_dev_strict_keyset_stats(uint64_t out[3], void* stream);
  * (status 0 without the ladder), out[3] = items sent on to the triage and the ladder (all of
  * them when the path is off). Waits for `stream` first. All zero before the first launch. */
 int nw_dev_strict_comb_stats(uint64_t out[4], void* stream);
+/* The same launch's items that the comb check did not pass but decided (its sum R' = [s]B - [k]A
+ * ran and R' is not the point R encodes; NW_STRICT_COMB_DECIDE=0 turns the decision off): out[0] =
+ * items the triage settled as NW_ERR_EQUATION from that verdict, without the ladder, out[1] =
+ * items handed to the ladder; both summed over the slices. They are among out[3] of
+ * nw_dev_strict_comb_stats. Waits for `stream` first. Both zero before the first launch and when
+ * the comb path is off. Tests and tools only. */
+int nw_dev_strict_decided_stats(uint64_t out[2], void* stream);
 /* Registered signers: keys that sign most of what a caller sends (a network's primaries, workers
  * and clients) keep their 8-bit comb tables (528 KB per key) on the device across calls, so
  * their items take the comb check in every unkeyed strict launch, whatever its size

@@ -66,6 +66,7 @@ def lib() -> ctypes.CDLL:
         "nw_dev_verify_strict_many": ([P, S, P, P, S, P, P, P], I),
         "nw_dev_strict_keyset_stats": ([P, P], I),
         "nw_dev_strict_comb_stats": ([P, P], I),
+        "nw_dev_strict_decided_stats": ([P, P], I),
         "nw_strict_signers_set": ([P, S], I),
         "nw_strict_signers_count": ([P], I),
         "nw_dev_strict_signers_stats": ([P, P], I),

@@ -314,6 +314,15 @@ int nw_dev_strict_comb_stats(uint64_t out[4], void* stream) {
   return 0;
 }
 
+int nw_dev_strict_decided_stats(uint64_t out[2], void* stream) {
+  DevCtx* c;
+  int rc = begin(&c);
+  if (rc) return rc;
+  if (!out) return set_err(NW_E_INVALID_ARG, "null pointer");
+  NW_HIP(nw::strict_decided_stats(out, pick_stream(stream, c)), "strict decided statistics");
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------
 // The registered signers of a device (DESIGN.md 5 "Round 10").
 namespace {

@@ -126,9 +126,12 @@ struct strict_ws_t {
 // The comb check for a call's hot keys (DESIGN.md 5 "Round 9"): a key of the slice's set used
 // by at least NW_STRICT_COMB_MIN items (default 256) that decodes and is not small gets 8-bit
 // comb tables j * 2^(8 t) A (keyspec_for(8): 32 tables of 129 entries, 528 KB) for the call,
-// and its items run keyed_vote_check (additions only, R never decompressed); everything the
-// check does not pass goes through the triage and the ladder as before, from a compacted
-// list. NW_STRICT_COMB=0 turns the path off; hot keys per slice are limited to
+// and its items run keyed_vote_check_ex (additions only, R never decompressed); everything the
+// check does not pass goes through the triage from a compacted list. An item that left the
+// check before its comb sum then takes the ladder as before; one whose sum ran and gave
+// R' != decode(R) carries that verdict in its list entry, and the triage settles it (R does not
+// decode, or NW_ERR_EQUATION) without the ladder (NW_STRICT_COMB_DECIDE=0, read per launch:
+// every listed item takes the ladder again). NW_STRICT_COMB=0 turns the path off; hot keys per slice are limited to
 // hot_cap = min(NW_STRICT_COMB_KEYS (default 8192), slice / min). All three are read per
 // launch. The path's allocation (tables, per-slot counts and indices, the to-do list) is
 // apart from the triage region's.
@@ -144,6 +147,10 @@ size_t strict_comb_bytes(uint64_t slice, uint64_t key_slots, uint64_t hot_cap);
 // For the last unkeyed two-pass launch queued on the current device: hot keys tabulated, items
 // checked by the comb, items it passed, items sent on to the triage. Synchronises `stream`.
 hipError_t strict_comb_stats(uint64_t out[4], hipStream_t stream);
+// Of the items sent on, for the same launch (DESIGN.md 5 "Round 11"): items the triage settled as
+// NW_ERR_EQUATION from the comb's verdict, items handed to the ladder (k_verify_strict_pre). Both
+// 0 when the comb path was off. Synchronises `stream`.
+hipError_t strict_decided_stats(uint64_t out[2], hipStream_t stream);
 // For the last unkeyed two-pass launch queued on the current device: distinct keys tabulated,
 // items that read a shared table, items on their own path. Synchronises `stream`.
 hipError_t strict_keyset_stats(uint64_t out[3], hipStream_t stream);

@@ -365,6 +365,9 @@ __global__ __launch_bounds__(256, NW_STRICT_WAVES) void k_verify_strict(const ui
 // 201-202, then dalek's verify_strict), and appends the others to a list with the x of A and
 // R; k_verify_strict_pre runs strict_verify_core on the list, loading those points instead
 // of decompressing them (strict_src_pre). Statuses are the same codes for every item.
+// With the comb path's to-do list an entry may say that the comb check decided its item
+// (kTodoDecided: R' = [s]B - [k]A is not the point R encodes): the triage then settles it, as
+// NW_ERR_EQUATION unless its own checks reject it, and the list never sees it.
 #ifndef NW_TRIAGE_WAVES
 #define NW_TRIAGE_WAVES 4   // waves per SIMD (129 VGPRs unbounded: 3)
 #endif
@@ -375,10 +378,14 @@ __global__ __launch_bounds__(256, NW_TRIAGE_WAVES) void k_strict_triage(
     uint32_t* __restrict__ count, const uint32_t* __restrict__ keyslot,
     const uint32_t* __restrict__ kflags, const uint32_t* __restrict__ todo,
     const uint32_t* __restrict__ todo_count, unsigned long long* __restrict__ todo_total,
-    const uint32_t* __restrict__ nhot) {
+    const uint32_t* __restrict__ nhot, unsigned long long* __restrict__ settled) {
   // todo == nullptr, or no hot key in the slice (*nhot == 0: the comb kernels did nothing):
-  // lane q takes item q of the slice; else item todo[q], q < *todo_count (the items the comb
-  // check left undecided, k_strict_todo_list)
+  // lane q takes item q of the slice; else the item of entry todo[q], q < *todo_count (the items
+  // the comb check did not pass, k_strict_todo_list). An entry with kTodoDecided set is an item
+  // whose comb sum ran and gave R' != decode(R): its status is the triage's own if the triage
+  // rejects it (R does not decode), else NW_ERR_EQUATION (comb_settled_status); either way it is
+  // settled here and never reaches the ladder. settled[wave & (kCombStatLanes - 1)] += the
+  // wave's items settled as equation failures (diagnostics, one atomic per wave that has any).
   const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (todo && *nhot == 0) todo = nullptr;
   const uint64_t nq = todo ? (uint64_t)*todo_count : ns;
@@ -386,7 +393,9 @@ __global__ __launch_bounds__(256, NW_TRIAGE_WAVES) void k_strict_triage(
   // *todo_total += the slice's items that come here (diagnostics, kept over a launch's slices)
   if (todo_total && q == 0) atomicAdd(todo_total, (unsigned long long)nq);
   if (__ballot(active) == 0) return;
-  const uint64_t j = todo ? (uint64_t)todo[active ? q : 0] : q;
+  const uint32_t entry = todo ? todo[active ? q : 0] : (uint32_t)q;
+  const bool decided = todo && (entry & kTodoDecided) != 0;
+  const uint64_t j = todo ? (uint64_t)comb_todo_item(entry) : q;
   const uint64_t i = i0 + (active ? j : 0);
   const strict_src_global src{pks + 8 * i, sigs + 16 * i, msgs + (uint64_t)msg_stride_words * i};
   // the key's slot in the slice's set (keyslot == nullptr: the set is off); an idle lane of the
@@ -396,11 +405,18 @@ __global__ __launch_bounds__(256, NW_TRIAGE_WAVES) void k_strict_triage(
   fe xa, xr;
   const int st = strict_triage(src, g_consts.sk, xa, xr, keyflags,
                                [](bool b) { return __ballot(b) != 0; });
-  if (active && st != NW_OK) status[i] = st;
-  const bool keep = active && st == NW_OK;
+  // (comb_settled_status of a rejected item is the triage's status, decided or not)
+  if (active && (st != NW_OK || decided)) status[i] = comb_settled_status(st);
+  const uint32_t lane = threadIdx.x & 63u;
+  if (todo) {
+    const uint64_t ms = __ballot(active && decided && st == NW_OK);
+    if (ms && lane == (uint32_t)__builtin_ctzll(ms))
+      atomicAdd(settled + ((q >> 6) & (kCombStatLanes - 1)),
+                (unsigned long long)__builtin_popcountll(ms));
+  }
+  const bool keep = active && st == NW_OK && !decided;
   const uint64_t m = __ballot(keep);
   if (m == 0) return;
-  const uint32_t lane = threadIdx.x & 63u;
   const uint32_t rank = (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull));
   const uint32_t leader = (uint32_t)__builtin_ctzll(m);
   uint32_t base = 0;
@@ -543,8 +559,13 @@ __global__ __launch_bounds__(256, NW_STRICT_WAVES) void k_verify_strict_pre(
     const uint32_t* __restrict__ sigs, uint64_t i0, const uint32_t* __restrict__ list,
     const uint32_t* __restrict__ count, const uint32_t* __restrict__ xs, uint64_t cap,
     int32_t* __restrict__ status, ge_cached_pk* __restrict__ tabs,
-    const ge_niels_pad* __restrict__ btw, const ge_cached_pk* __restrict__ ktabs) {
+    const ge_niels_pad* __restrict__ btw, const ge_cached_pk* __restrict__ ktabs,
+    unsigned long long* __restrict__ ladder_total) {
   const uint64_t n = *count;
+  // *ladder_total (optional) += the slice's items that come here (diagnostics, kept over a
+  // launch's slices: one atomic per slice)
+  if (ladder_total && n && blockIdx.x == 0 && threadIdx.x == 0)
+    atomicAdd(ladder_total, (unsigned long long)n);
 #if NW_BWIN == 8
   __shared__ ge_niels s_btab[129];
   __shared__ ge_niels s_b128[129];
@@ -590,7 +611,10 @@ __global__ __launch_bounds__(256, NW_STRICT_WAVES) void k_verify_strict_pre(
 // HOT = false: a committee's tables, item i's key is vote_key[vk0 + i]. HOT = true: the call's
 // hot keys (launch_verify_strict's comb path): vote_key[vk0 + i] is the item's slot in the
 // slice's key set and slotmap[slot] its key's index in the call's 8-bit tables (or kNoKey),
-// valid below *nlive; *checked += items with a key. NW_COMB_WAVES: waves per SIMD of the HOT
+// valid below *nlive; *checked += items with a key. There the state also tells the two kinds of
+// failure apart (kVoteFail / kVoteDecided, strict_keyed_item below): k_strict_todo_list hands a
+// decided item's verdict to the triage, which settles it without the ladder (DESIGN.md 5
+// "Round 11"); the committee branch lists both kinds alike for k_verify_strict. NW_COMB_WAVES: waves per SIMD of the HOT
 // instance (1 to 4 measured alike on config 4; the LDS prefetcher measured 4 % slower there,
 // as it did for committee tables: DESIGN.md 5 "Round 9").
 #ifndef NW_COMB_WAVES
@@ -598,7 +622,9 @@ __global__ __launch_bounds__(256, NW_STRICT_WAVES) void k_verify_strict_pre(
 #endif
 // The check of slice item i (global item gi) under the key whose comb tables are `tab` and whose
 // flag word is *okword (tab == nullptr: the item has no key here) and what it leaves behind:
-// status 0 for a pass, X' / Z' in the planes for a pending parity, the state word.
+// status 0 for a pass, X' / Z' in the planes for a pending parity, the state word: kVoteFail
+// for an item without a key or one that left the check before the comb sum, kVoteDecided for
+// one whose sum ran and gave Y' != y_R Z' (nw_strict.hpp keyed_vote_check_ex).
 __device__ __forceinline__ void strict_keyed_item(
     const uint32_t* __restrict__ msgs, uint32_t msg_stride_words, const uint32_t* __restrict__ pks,
     const uint32_t* __restrict__ sigs, uint64_t gi, uint64_t i, int32_t* __restrict__ status,
@@ -609,7 +635,8 @@ __device__ __forceinline__ void strict_keyed_item(
     const strict_src_global src{pks + 8 * gi, sigs + 16 * gi,
                                 msgs + (uint64_t)msg_stride_words * gi};
     fe X, Z;
-    st = keyed_vote_check(src, g_consts.sk, bcomb_wide{bcomb}, keytab_wide{tab, ks}, *okword, X, Z);
+    st = keyed_vote_check_ex(src, g_consts.sk, bcomb_wide{bcomb}, keytab_wide{tab, ks}, *okword, X,
+                             Z);
     if (st >= kVotePending) {
 #pragma unroll
       for (int k = 0; k < 10; ++k) {
@@ -675,7 +702,8 @@ __global__ __launch_bounds__(256, NW_COMB_WAVES) void k_strict_keyed_signers(
 }
 
 // Parity of the pending items (Montgomery's trick per strided chunk, as k_votes_keyed_inv):
-// a match is status 0, a mismatch goes to the list.
+// a match is status 0, a mismatch goes to the list as kVoteDecided (R' = -decode(R): the
+// equation fails whatever else the full verification would look at).
 __global__ __launch_bounds__(256) void k_strict_keyed_inv(uint64_t i0, uint64_t ns,
                                                           uint64_t nchunks,
                                                           int32_t* __restrict__ status,
@@ -714,8 +742,9 @@ __global__ __launch_bounds__(256) void k_strict_keyed_inv(uint64_t i0, uint64_t 
       load(W, 0, i);
       load(Z, 10, i);
       fe_mul(x, W, inv);
-      if (fe_isnegative(x) != (st & 1)) vp.state[i] = kVoteFail;
-      else status[i0 + i] = NW_OK;
+      const bool match = fe_isnegative(x) == (st & 1);
+      if (match) status[i0 + i] = NW_OK;
+      else vp.state[i] = comb_parity_state(false);
       fe_mul(inv, inv, Z);
     }
     if (i < nchunks) break;
@@ -728,7 +757,7 @@ __global__ __launch_bounds__(256) void k_strict_keyed_list(uint64_t i0, uint64_t
                                                            uint32_t* __restrict__ list,
                                                            uint32_t* __restrict__ count) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const bool f = i < ns && state[i] == kVoteFail;
+  const bool f = i < ns && vote_failed(state[i]);   // kVoteDecided is listed like kVoteFail
   const uint64_t m = __ballot(f);
   if (m == 0) return;
   const uint32_t lane = threadIdx.x & 63;
@@ -743,24 +772,32 @@ __global__ __launch_bounds__(256) void k_strict_keyed_list(uint64_t i0, uint64_t
 // block takes kTodoPer x 256 consecutive items and appends its failed ones with ONE atomic
 // (a slice of 12.5M items with ~10 % of them failed: one atomic per wave was ~195 k
 // same-address atomics, 4.6 ms).
+// Both kinds of failure are listed. The triage cannot read an item's state (plane 20 at the
+// item's index: it overwrites planes 0-20+ at the list positions of other items while it runs),
+// so the entry carries it: bit 31 (comb_todo_entry) for kVoteDecided when `decide` is set
+// (NW_STRICT_COMB_DECIDE, default on; off: every entry is plain, the sequence of rounds 9-10).
 constexpr uint32_t kTodoPer = 16;
 __global__ __launch_bounds__(256) void k_strict_todo_list(uint64_t ns,
                                                           const uint32_t* __restrict__ state,
                                                           uint32_t* __restrict__ list,
                                                           uint32_t* __restrict__ count,
-                                                          const uint32_t* __restrict__ nlive) {
+                                                          const uint32_t* __restrict__ nlive,
+                                                          uint32_t decide) {
   __shared__ uint32_t s_wave[4];
   __shared__ uint32_t s_base;
   if (*nlive == 0) return;   // no hot key, no state: the triage takes the whole slice
   const uint64_t b0 = (uint64_t)blockIdx.x * (256 * kTodoPer);
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   // round r: items b0 + 256 r + threadIdx.x; this wave's failed items of all rounds, counted
-  uint64_t masks[kTodoPer];
+  // (dmasks: those of them that are kVoteDecided)
+  uint64_t masks[kTodoPer], dmasks[kTodoPer];
   uint32_t mine = 0;
 #pragma unroll
   for (uint32_t r = 0; r < kTodoPer; ++r) {
     const uint64_t i = b0 + 256 * r + threadIdx.x;
-    masks[r] = __ballot(i < ns && state[i] == kVoteFail);
+    const uint32_t st = i < ns ? state[i] : kVotePass;
+    masks[r] = __ballot(vote_failed(st));
+    dmasks[r] = __ballot(st == kVoteDecided);
     mine += (uint32_t)__builtin_popcountll(masks[r]);
   }
   if (lane == 0) s_wave[wave] = mine;
@@ -777,13 +814,14 @@ __global__ __launch_bounds__(256) void k_strict_todo_list(uint64_t ns,
     const uint64_t m = masks[r];
     if ((m >> lane) & 1ull)
       list[pos + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull))] =
-          (uint32_t)(b0 + 256 * r + threadIdx.x);
+          comb_todo_entry((uint32_t)(b0 + 256 * r + threadIdx.x),
+                          ((dmasks[r] >> lane) & 1ull) ? kVoteDecided : kVoteFail, decide != 0);
     pos += (uint32_t)__builtin_popcountll(m);
   }
 }
 
 // Diagnostics of a slice that ran k_strict_keyed_signers, after k_strict_keyed_inv (an item the
-// comb passed is any checked item whose state is not kVoteFail): ctr[c][lane] += the block's
+// comb passed is any checked item whose state is neither kVoteFail nor kVoteDecided): ctr[c][lane] += the block's
 // items c = 0 checked, 1 checked under a registered key, 2 passed under one. A block takes
 // kTodoPer x 256 consecutive items and adds each of its sums with ONE atomic, spread over
 // kCombStatLanes addresses.
@@ -804,7 +842,7 @@ __global__ __launch_bounds__(256) void k_strict_signers_count(
       const uint32_t kk = slot != kNoSlot ? slotmap[slot] : kNoKey;
       reg = kk < nreg;
       any = reg || (kk != kNoKey && kk - nreg < *nhot);
-      pass = reg && state[i] != kVoteFail;
+      pass = reg && !vote_failed(state[i]);
     }
     mine[0] += (uint32_t)__builtin_popcountll(__ballot(any));
     mine[1] += (uint32_t)__builtin_popcountll(__ballot(reg));
@@ -1309,6 +1347,8 @@ size_t strict_workspace_bytes() { return strict_tabs_bytes() + strict_keyed_regi
 // large: config 4 is one slice, so the second pass's last, partly filled round over the
 // resident lanes comes once per launch.
 constexpr uint64_t kTriageSlice = 1ull << 24;
+static_assert(kTriageSlice <= (uint64_t)kTodoDecided,
+              "a to-do entry holds the slice item below bit 31 (comb_todo_entry)");
 uint64_t strict_triage_slice(uint64_t n) {
   if (!strict_triage_on()) return 0;
   uint64_t lim = kTriageSlice;
@@ -1353,13 +1393,16 @@ strict_comb_plan_t strict_comb_plan(uint64_t slice, uint64_t key_slots) {
 // The path's allocation: a kCombBlockBytes block (the slice's words: nhot, the to-do count and
 // nlive = hot keys + registered keys in the slice, kCombSliceBytes in all; then the launch's
 // counters, 64 bits each: hot keys, items checked, items listed from kCombStatsAt, registered
-// keys matched after them, and from kCombLanesAt 3 x kCombStatLanes of
-// k_strict_signers_count), the to-do list (a word per item of the slice), per slot of the key
+// keys matched and items handed to the ladder after them, and from kCombLanesAt 3 x
+// kCombStatLanes of k_strict_signers_count and kCombStatLanes of the triage's settled items),
+// the to-do list (a word per item of the slice), per slot of the key
 // set its uses, its hot index and its registry row, per hot key its owner's row and its flags,
 // then the tables (key_tables_bytes).
 namespace {
 constexpr uint64_t kCombSliceBytes = 16, kCombStatsAt = 16, kCombLanesAt = 1024;
-static_assert(kCombLanesAt + 8 * 3 * kCombStatLanes <= kCombBlockBytes, "the block's counters");
+static_assert(kCombStatsAt + 8 * 5 <= kCombLanesAt &&
+                  kCombLanesAt + 8 * 4 * kCombStatLanes <= kCombBlockBytes,
+              "the block's counters");
 struct comb_region_t {
   uint64_t todo, uses, hotidx, match, hotrow, hok, tabs, bytes;
 };
@@ -1416,6 +1459,27 @@ hipError_t strict_comb_stats(uint64_t out[4], hipStream_t stream) {
   for (uint32_t t = 0; t < kCombStatLanes; ++t) out[1] += h[kCombLanesAt / 8 + t];
   out[3] = c[2];
   out[2] = rec.n - c[2];   // every item is either passed by the comb or listed
+  return hipSuccess;
+}
+hipError_t strict_decided_stats(uint64_t out[2], hipStream_t stream) {
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  keyset_record_t rec;
+  {
+    std::lock_guard<std::mutex> g(g_keyset_m);
+    if (dev >= 0 && dev < 64) rec = g_keyset_last[dev];
+  }
+  out[0] = out[1] = 0;
+  if (!rec.valid) return hipSuccess;
+  e = hipStreamSynchronize(stream);
+  if (e != hipSuccess || !rec.comb) return e;
+  std::vector<unsigned long long> h(kCombBlockBytes / 8);
+  e = hipMemcpy(h.data(), rec.comb, kCombBlockBytes, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return e;
+  for (uint32_t t = 0; t < kCombStatLanes; ++t)
+    out[0] += h[kCombLanesAt / 8 + 3 * kCombStatLanes + t];
+  out[1] = h[kCombStatsAt / 8 + 4];
   return hipSuccess;
 }
 hipError_t strict_signers_stats(uint64_t out[3], hipStream_t stream) {
@@ -1545,6 +1609,10 @@ hipError_t launch_verify_strict(const uint32_t* msgs, uint32_t msg_stride_words,
   if (eb == hipSuccess && kt.vote_key) eb = btab_for_current_device(1, &bcomb);
   if (eb != hipSuccess) return eb;
   const char* kf = getenv("NW_STRICT_KEYED_FAST");
+  // NW_STRICT_COMB_DECIDE=0: the comb path's to-do entries carry no verdict, so every listed
+  // item that survives the triage takes the ladder (rounds 9-10's sequence; A/B hook)
+  const char* cd = getenv("NW_STRICT_COMB_DECIDE");
+  const uint32_t comb_decide = !(cd && cd[0] == '0');
   // the comb check of the call's hot keys needs its allocation (Lease::strict_ws) and the B
   // comb; without either the launch runs without it
   // (with registered signers the path runs even without room for call-local tables)
@@ -1637,7 +1705,8 @@ hipError_t launch_verify_strict(const uint32_t* msgs, uint32_t msg_stride_words,
       if (comb_on) {
         // the slice's hot keys and their 8-bit comb tables, then the comb check of their items:
         // a pass is status 0 (k_strict_keyed, or k_strict_keyed_inv for the x parity); every
-        // other item of the slice goes on the to-do list. X' / Z' and the state use the
+        // other item of the slice goes on the to-do list, with the comb's verdict in the entry
+        // when its sum ran (the triage then settles the item without the ladder). X' / Z' and the state use the
         // region's planes 0-20, which the triage overwrites afterwards.
         if (reg_on)
           hipLaunchKernelGGL(k_strict_signers_match, dim3(grid_for(kcap, 256)), dim3(256), 0,
@@ -1667,16 +1736,18 @@ hipError_t launch_verify_strict(const uint32_t* msgs, uint32_t msg_stride_words,
           hipLaunchKernelGGL(k_strict_signers_count, dim3(grid_for(ns, 256 * kTodoPer)), dim3(256),
                              0, stream, ns, keyslot, hotidx, nhot, nlive, sg.n, vp.state, lanes);
         hipLaunchKernelGGL(k_strict_todo_list, dim3(grid_for(ns, 256 * kTodoPer)), dim3(256), 0,
-                           stream, ns, vp.state, todo, tcount, nlive);
+                           stream, ns, vp.state, todo, tcount, nlive, comb_decide);
       }
       hipLaunchKernelGGL(k_strict_triage, dim3(grid_for(ns, 256)), dim3(256), 0, stream, msgs,
                          msg_stride_words, pks, sigs, i0, ns, status, xs, slice, list, count,
                          keyslot, kflags, comb_on ? todo : nullptr, tcount,
-                         comb_on ? cstats + 2 : nullptr, nlive);
+                         comb_on ? cstats + 2 : nullptr, nlive,
+                         comb_on ? lanes + 3 * kCombStatLanes : nullptr);
       hipLaunchKernelGGL(k_verify_strict_pre,
                          dim3(std::min<uint64_t>(strict_grid(), grid_for(ns, 256))), dim3(256),
                          0, stream, msgs, msg_stride_words, pks, sigs, i0, list, count, xs,
-                         slice, status, static_cast<ge_cached_pk*>(workspace), btw, ktabs);
+                         slice, status, static_cast<ge_cached_pk*>(workspace), btw, ktabs,
+                         comb_on ? cstats + 4 : nullptr);
     }
     if (bitmap)
       hipLaunchKernelGGL(k_status_bitmap, dim3(grid_for(n, 256)), dim3(256), 0, stream, status,

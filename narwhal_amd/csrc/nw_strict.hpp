@@ -708,11 +708,37 @@ NW_HD void keyed_comb_sum(ge& acc, const sc& k, const sc& s, const BComb& bc,
 // (sign ? -x0 : x0, y_R)); R' == decode(R) then iff x0 == 0 (X' == 0) or the parity of
 // X'/Z' equals the sign bit. Returns kVotePass / kVoteFail, or kVotePending (| sign) when
 // only that parity is left: the caller batches the inversions of Z' (k_votes_keyed_inv).
-constexpr uint32_t kVotePass = 0, kVoteFail = 1, kVotePending = 2;
+//
+// keyed_vote_check_ex tells the two kinds of failure apart (the strict launch's comb path,
+// DESIGN.md 5 "Round 11"): kVoteFail for an exit before the comb sum (undecided: which check
+// fails is for the caller's full verification to say), kVoteDecided once the sum ran and
+// Y' != y_R Z'. Then s has no high bits and is canonical, A decodes and is not small, R's y is
+// not a small-order y and R' != decode(R) whenever R decodes: in strict_verify_core's order only
+// "R does not decode" can still come before NW_ERR_EQUATION. keyed_vote_check is the same check
+// with both kinds reported as kVoteFail (the certificate votes, which only ask pass or fail).
+// kVoteDecided is below kVotePending, so `>= kVotePending` still means "parity left".
+constexpr uint32_t kVotePass = 0, kVoteFail = 1, kVoteDecided = 2, kVotePending = 4;
+// A state word that stands for a failure of either kind.
+NW_HD bool vote_failed(uint32_t st) { return st == kVoteFail || st == kVoteDecided; }
+// The state of a pending item once the parity of X'/Z' is known (k_strict_keyed_inv): a mismatch
+// is R' = -decode(R) with x0 != 0, decided like Y' != y_R Z'.
+NW_HD uint32_t comb_parity_state(bool match) { return match ? kVotePass : kVoteDecided; }
+// The comb path's to-do entry of slice item j (k_strict_todo_list; j < 2^31): bit 31 tells the
+// triage that the comb check decided the item (`decide`: NW_STRICT_COMB_DECIDE is not 0).
+constexpr uint32_t kTodoDecided = 1u << 31;
+NW_HD uint32_t comb_todo_entry(uint32_t j, uint32_t state, bool decide) {
+  return j | (decide && state == kVoteDecided ? kTodoDecided : 0u);
+}
+NW_HD uint32_t comb_todo_item(uint32_t entry) { return entry & ~kTodoDecided; }
+// The status of a decided item from its triage status (strict_triage): the triage's own when it
+// rejects the item (R does not decode; nothing else can be left), else the equation's.
+NW_HD int comb_settled_status(int triage_status) {
+  return triage_status != NW_OK ? triage_status : NW_ERR_EQUATION;
+}
 template <class BComb, class KeyTab, class Src, class PF = pf_none>
-NW_HD uint32_t keyed_vote_check(const Src& src, const strict_consts& K, const BComb& bc,
-                                const KeyTab& keytab, uint32_t keyflags, fe& X, fe& Z,
-                                const PF& pf = PF{}) {
+NW_HD uint32_t keyed_vote_check_ex(const Src& src, const strict_consts& K, const BComb& bc,
+                                   const KeyTab& keytab, uint32_t keyflags, fe& X, fe& Z,
+                                   const PF& pf = PF{}) {
   const bool okA = (keyflags & kKeyDecoded) != 0, smallA = (keyflags & kKeySmall) != 0;
   // a key with a torsion component: a strict pass does not make its batch term vanish
   // (dalek weights A by z k mod l), so its votes take the certificate's own verify_batch
@@ -738,11 +764,18 @@ NW_HD uint32_t keyed_vote_check(const Src& src, const strict_consts& K, const BC
   keyed_comb_sum(acc, k, s, bc, keytab, K.k.d2, pf);
   fe t;
   fe_mul(t, yR, acc.Z);
-  if (!fe_eq(t, acc.Y)) return kVoteFail;
+  if (!fe_eq(t, acc.Y)) return kVoteDecided;
   if (fe_iszero(acc.X)) return kVotePass;
   fe_copy(X, acc.X);
   fe_copy(Z, acc.Z);
   return kVotePending | sign;
+}
+template <class BComb, class KeyTab, class Src, class PF = pf_none>
+NW_HD uint32_t keyed_vote_check(const Src& src, const strict_consts& K, const BComb& bc,
+                                const KeyTab& keytab, uint32_t keyflags, fe& X, fe& Z,
+                                const PF& pf = PF{}) {
+  const uint32_t st = keyed_vote_check_ex(src, K, bc, keytab, keyflags, X, Z, pf);
+  return st == kVoteDecided ? kVoteFail : st;
 }
 
 // Keyed strict verification: A is a committee key with comb tables j * 2^(W t) A

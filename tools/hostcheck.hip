@@ -403,11 +403,13 @@ struct src_arrays_keys : src_arrays_pre_scalars {
 };
 extern "C++" {
 template <int BW, class BTab>
-static int keyset_item(src_arrays_keys& src, const BTab& bt, uint32_t slot, const uint32_t* kflags) {
+static int keyset_item(src_arrays_keys& src, const BTab& bt, uint32_t slot, const uint32_t* kflags,
+                       bool* laddered = nullptr) {
   const uint32_t keyflags = slot != kNoSlot ? kflags[slot] : kNoSlot;
   for (int t = 0; t < 10; ++t) src.xa.v[t] = 0xdeadbeefu;
   const int st = strict_triage(static_cast<const strict_src_arrays&>(src), SK, src.xa, src.xr,
                                keyflags, [](bool b) { return b; });
+  if (laddered) *laddered = st == NW_OK;
   if (st != NW_OK) return st;
   if (slot != kNoSlot) src.xa.v[0] = slot;
   strict_triage_scalars<BW>(static_cast<const strict_src_arrays&>(src), src.words,
@@ -538,6 +540,103 @@ int hc_verify_strict_comb_many(const uint8_t* pks, const uint8_t* sigs, const ui
         : keyset_item<16>(src, btab_wide{BTW, BTW_N}, keyslot[j], kflags.data());
   }
   if (stats) { stats[0] = hotA.size(); stats[1] = checked; stats[2] = passed; stats[3] = n - passed; }
+  return 0;
+}
+
+// The same slice with the comb's verdict carried to the triage (DESIGN.md 5 "Round 11"), step
+// for step as the kernels take it: keyed_vote_check_ex and comb_parity_state give the item's
+// state word (k_strict_keyed<true>, k_strict_keyed_inv), comb_todo_entry its to-do entry
+// (k_strict_todo_list; decide = 0 is NW_STRICT_COMB_DECIDE=0), and a listed item is what
+// k_strict_triage makes of the entry: strict_triage and comb_settled_status for a decided one,
+// keyset_item (triage, scalars, ladder) for any other. path_out[j] says where item j's status
+// came from: 0 the comb passed it, 1 settled by the triage from the comb's verdict, 2 the ladder,
+// 3 rejected by the triage undecided; | 16: under a hot key, | 32: its comb sum ran. stats as
+// hc_verify_strict_comb_many; dstats: items settled as NW_ERR_EQUATION, items through the ladder.
+int hc_verify_strict_decided_many(const uint8_t* pks, const uint8_t* sigs, const uint8_t* k32,
+                                  uint32_t n, uint64_t key_slots, int bw, uint32_t comb_min,
+                                  uint32_t comb_keys, int decide, int32_t* status_out,
+                                  uint8_t* path_out, uint64_t stats[4], uint64_t dstats[2]) {
+  init();
+  if (n == 0) return 0;
+  const uint64_t slice = ((uint64_t)n + 63) & ~63ull;
+  const uint32_t cap = (uint32_t)strict_keys_plan(key_slots, slice);
+  std::vector<uint32_t> keyslot(n), slots(cap), kflags(cap), uses(cap), hotidx(cap, kNoKey);
+  std::vector<ge_cached_pk> ktabs(8 * (size_t)cap);
+  std::vector<uint32_t> pkw(8 * (size_t)n);
+  memcpy(pkw.data(), pks, 32 * (size_t)n);
+  uint32_t nkeys = 0;
+  for (uint32_t j = 0; j < n; ++j) {
+    keyslot[j] = cap ? keyset_probe(slots.data(), cap, cap / 2, &nkeys, pkw.data(), 0, j,
+                                    plain_atomics{})
+                     : kNoSlot;
+    if (keyslot[j] != kNoSlot && comb_sampled(j)) uses[keyslot[j]] += kCombSample;
+  }
+  for (uint32_t s = 0; s < cap; ++s)
+    keyset_build(slots.data(), s, pkw.data(), 0, SK, kflags.data(), ktabs.data());
+  const uint64_t hot_cap = comb_min ? std::min<uint64_t>(comb_keys, slice / comb_min) : 0;
+  std::vector<ge> hotA;
+  for (uint32_t s = 0; s < cap && hotA.size() < hot_cap; ++s) {
+    if (slots[s] == 0 || !comb_key_hot(uses[s], comb_min, kflags[s])) continue;
+    ge A;
+    if (!ge_frombytes(A, pkw.data() + 8 * (size_t)(slots[s] - 1), K)) return -2;
+    hotidx[s] = (uint32_t)hotA.size();
+    hotA.push_back(A);
+  }
+  uint64_t checked = 0, passed = 0, settled = 0, ladder = 0;
+  const keyspec ks8 = keyspec_for(8);
+  for (uint32_t j = 0; j < n; ++j) {
+    uint32_t Aw[8], Rw[8], Sw[8], kw[8];
+    load8(Aw, pks + 32 * (size_t)j); load8(Rw, sigs + 64 * (size_t)j);
+    load8(Sw, sigs + 64 * (size_t)j + 32); load8(kw, k32 + 32 * (size_t)j);
+    const uint32_t h = keyslot[j] != kNoSlot ? hotidx[keyslot[j]] : kNoKey;
+    // the state word: no hot key in the slice leaves the whole slice to the triage, unlisted
+    uint32_t state = kVoteFail;
+    uint8_t where = 0;
+    if (h != kNoKey) {
+      ++checked;
+      where |= 16;
+      const strict_src_arrays src{Aw, Rw, Sw, kw};
+      fe X, Z;
+      state = keyed_vote_check_ex(src, SK, bcomb_lazy{BT, &SK.k.d2},
+                                  keytab_lazy{&hotA[h], &SK.k.d2, ks8}, kKeyDecoded, X, Z);
+      if (state != kVoteFail) where |= 32;
+      if (state >= kVotePending) {
+        fe zi, x;
+        fe_invert(zi, Z);
+        fe_mul(x, X, zi);
+        state = comb_parity_state(fe_isnegative(x) == (state & 1));
+      }
+      if (state == kVotePass) {
+        status_out[j] = NW_OK;
+        if (path_out) path_out[j] = where;
+        ++passed;
+        continue;
+      }
+    }
+    const uint32_t entry = hotA.empty() ? j : comb_todo_entry(j, state, decide != 0);
+    src_arrays_keys src{};
+    src.a = Aw; src.r = Rw; src.s = Sw; src.k = kw;
+    src.ktabs = ktabs.data();
+    const uint32_t slot = keyslot[comb_todo_item(entry)];
+    if (entry & kTodoDecided) {
+      const int st = strict_triage(static_cast<const strict_src_arrays&>(src), SK, src.xa, src.xr,
+                                   slot != kNoSlot ? kflags[slot] : kNoSlot,
+                                   [](bool b) { return b; });
+      status_out[j] = comb_settled_status(st);
+      settled += st == NW_OK;
+      where |= 1;
+    } else {
+      bool laddered = false;
+      status_out[j] = bw == -24
+          ? keyset_item<24>(src, btab_lazy_entry{{BT, &SK.k.d2}, {}}, slot, kflags.data(), &laddered)
+          : keyset_item<16>(src, btab_wide{BTW, BTW_N}, slot, kflags.data(), &laddered);
+      ladder += laddered;
+      where |= laddered ? 2 : 3;
+    }
+    if (path_out) path_out[j] = where;
+  }
+  if (stats) { stats[0] = hotA.size(); stats[1] = checked; stats[2] = passed; stats[3] = n - passed; }
+  if (dstats) { dstats[0] = settled; dstats[1] = ladder; }
   return 0;
 }
 

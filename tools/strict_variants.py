@@ -17,8 +17,13 @@ NW_STRICT_WAVES, NW_PF_SWAP, NW_ADD_NEGC.
 
 A variant may also be a run-time knob of one build: LIB@NAME=VALUE sets that environment
 variable around the variant's launches (knobs read per launch only: NW_STRICT_KEYS, the
-slots of the call's key set, 0 = off; NW_TRIAGE_SLICE), e.g.
+slots of the call's key set, 0 = off; NW_TRIAGE_SLICE; NW_STRICT_COMB_DECIDE, 0 = the comb
+check's verdict is not carried to the triage, every listed item takes the ladder), e.g.
     LIB LIB@NW_STRICT_KEYS=0
+--flood: every second item's message gets a flipped bit (a flood of wrong-message signatures
+under the corpus's keys: those items fail the equation under whatever key they carry).
+A library that has nw_dev_strict_decided_stats reports it for the variant's last launch
+(decided_stats: items the triage settled as equation failures, items handed to the ladder).
 --keys K: the corpus's signers (bench.py's config 4 has 4,096); K = 0: every item has a key
 of its own (then all items are valid: keys and signatures made on the device, no edits).
 --signers: every LIB becomes two variants of the same library and corpus, LIB#registered (the
@@ -100,6 +105,8 @@ def main():
                     help="tile only the corpus's valid items (no early-decided statuses)")
     ap.add_argument("--keys", type=int, default=4096,
                     help="signers of the corpus; 0 = a key per item (all valid)")
+    ap.add_argument("--flood", action="store_true",
+                    help="flip a message bit of every second item (wrong-message flood)")
     ap.add_argument("--signers", action="store_true",
                     help="each LIB as LIB#registered and LIB#cleared (nw_strict_signers_set)")
     ap.add_argument("--registered-only", action="store_true",
@@ -133,6 +140,9 @@ def main():
         m, p, s = (t.index_select(0, idx).contiguous() for t in (m_u, p_u, s_u))
         del idx
         exp = np.resize(valid, n)
+    if a.flood:
+        m[::2, :2] ^= 1   # two bits: the corpus's own wrong-message items flip one
+        exp[::2] = False
     variants = [split_variant(x.partition("#")[0]) for x in a.libs]
     signers = None
     if a.signers:   # the K most used keys of the corpus
@@ -150,6 +160,7 @@ def main():
     P = lambda t: ctypes.c_void_p(t.data_ptr())
     times = {x: [] for x in a.libs}
     ok = {}
+    decided = {}
     for rep in range(a.reps):
         for name, L, (_, env) in zip(a.libs, libs, variants):
             if a.signers:
@@ -196,6 +207,11 @@ def main():
                 e1.record()
             torch.cuda.synchronize()
             times[name] += [e0.elapsed_time(e1) for e0, e1 in evs]
+            if hasattr(L, "nw_dev_strict_decided_stats"):
+                d = (ctypes.c_uint64 * 2)()
+                L.nw_dev_strict_decided_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+                if L.nw_dev_strict_decided_stats(d, stream) == 0:
+                    decided[name] = [int(d[0]), int(d[1])]
     per = a.host_calls or a.steps
     if a.signers:
         for L in loaded.values():
@@ -206,7 +222,9 @@ def main():
                           "min_ms": float(np.min(times[name])),
                           "rep_medians_ms": [float(np.median(times[name][r * per:(r + 1) * per]))
                                              for r in range(a.reps)],
-                          "parity": ok[name]}), flush=True)
+                          "parity": ok[name],
+                          **({"decided_stats": decided[name]} if name in decided else {})}),
+              flush=True)
 
 
 if __name__ == "__main__":
