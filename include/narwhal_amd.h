@@ -244,7 +244,20 @@ int nw_dev_strict_decided_stats(uint64_t out[2], void* stream);
  * NW_STRICT_SIGNERS_MAX keys (default 8192: 4.3 GB; read at the call): NW_E_INVALID_ARG.
  * NW_E_OUT_OF_MEMORY leaves the set empty and the library usable. A launch of fewer than
  * NW_STRICT_SIGNERS_MIN_ITEMS items (default 1; read per launch) ignores the set, as does every
- * launch under NW_STRICT_COMB=0. */
+ * launch under NW_STRICT_COMB=0.
+ *
+ * The set also serves Signature::verify_batch through every host-buffer entry:
+ * nw_signature_verify_batch, nw_verify_batch_many, nw_submit_verify_batch_many and the service's
+ * nw_service_verify_batch jobs (each part of a call under NW_ALL_DEVICES alike). With a non-empty
+ * set every vote of such a call first takes the comb check under its registered key; a batch all
+ * of whose votes pass is Ok for every coefficient set and is settled there, every other batch
+ * (a vote that fails, a signer that is not registered, a registered key with a torsion component)
+ * runs the ordinary verify_batch, which names its status and failing index. No verdict depends on
+ * the set. NW_BATCH_SIGNERS=0 turns this off, NW_BATCH_SIGNERS_MIN_VOTES (default 1) is the
+ * smallest call that takes it (both read per call; NW_STRICT_COMB does not govern it). It needs
+ * the device's B comb table: where that cannot be allocated the calls run as without a set.
+ * Not served: nw_dev_verify_batch_many (the caller owns the workspace) and the Header / Vote /
+ * Certificate entries, which have their committee's tables. */
 int nw_strict_signers_set(const uint8_t* pks, size_t n);
 /* Registered keys on the current device. */
 int nw_strict_signers_count(uint64_t* n);
@@ -254,6 +267,12 @@ int nw_strict_signers_count(uint64_t* n);
  * nw_dev_strict_comb_stats, whose out[0] keeps counting call-local tables only and whose
  * out[1..3] count items whichever tables served them. */
 int nw_dev_strict_signers_stats(uint64_t out[3], void* stream);
+/* verify_batch calls under the registered signers, summed over the process since it started
+ * (every device; a call counts once its outputs have been delivered): out[0] = votes the comb
+ * check passed, out[1] = votes it did not pass, out[2] = batches settled by it (empty batches
+ * included), out[3] = batches sent on to the ordinary verify_batch. Calls that did not take the
+ * path count nothing. NW_E_NO_DEVICE without a device. */
+int nw_batch_signers_stats(uint64_t out[4]);
 
 /* ---- aggregation service: one request per message, coalesced into device jobs ------- */
 /* The front end a crypto-gpu crate puts behind the primary's per-message checks: Core

@@ -32,7 +32,7 @@ __all__ = ["Digest", "Hash", "PublicKey", "SecretKey", "Signature", "CryptoError
            "EngineError", "generate_keypair", "keypair_from_seed_many", "sign_many",
            "sha512_digest", "sha512_digest32_many", "verify_strict_many",
            "verify_batch_many", "set_strict_signers", "strict_signers_count",
-           "strict_signers_stats"]
+           "strict_signers_stats", "batch_signers_stats"]
 
 
 class CryptoError(Exception):
@@ -275,6 +275,15 @@ def strict_signers_stats(stream=None) -> tuple[int, int, int]:
     check(_lib.lib().nw_dev_strict_signers_stats(out, ctypes.c_void_p(stream)),
           "nw_dev_strict_signers_stats")
     return int(out[0]), int(out[1]), int(out[2])
+
+
+def batch_signers_stats() -> tuple[int, int, int, int]:
+    """(votes passed, votes not passed, batches settled, batches sent on) of the verify_batch
+    calls that took the comb check under the registered signers, summed over the process
+    (nw_batch_signers_stats); a call counts once its outputs have been delivered."""
+    out = (ctypes.c_uint64 * 4)()
+    check(_lib.lib().nw_batch_signers_stats(out), "nw_batch_signers_stats")
+    return int(out[0]), int(out[1]), int(out[2]), int(out[3])
 
 
 def verify_batch_many(digests: np.ndarray, pks: np.ndarray, sigs: np.ndarray,

@@ -1125,9 +1125,9 @@ int ReadLease::acquire(int dev_index, hipStream_t stream, const uint8_t* pks, si
   return 0;
 }
 
-int ReadLease::release() {
-  if (!held_) return 0;
-  SharedDev& d = g_shared[dev_];
+// Closes a reader's launches (ReadLease, SignersLease; d.m held): its completion event joins
+// d.readers, then the device is unlocked.
+static int reader_release(SharedDev& d, hipStream_t stream, const char* what) {
   hipEvent_t ev = nullptr;
   hipError_t e = hipSuccess;
   if (!d.rpool.empty()) {
@@ -1136,7 +1136,7 @@ int ReadLease::release() {
   } else {
     e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
   }
-  if (e == hipSuccess) e = hipEventRecord(ev, stream_);
+  if (e == hipSuccess) e = hipEventRecord(ev, stream);
   if (e == hipSuccess) {
     d.readers.push_back(ev);
     if (d.readers.size() > 32) {   // keep the list short: drop readers that have finished
@@ -1150,14 +1150,52 @@ int ReadLease::release() {
   } else if (ev) {
     d.rpool.push_back(ev);
   }
-  held_ = false;
   d.m.unlock();
   // without its event a later Lease could overwrite the tables under the launch: wait
   if (e != hipSuccess) {
-    (void)hipStreamSynchronize(stream_);
-    return ::set_err(NW_E_DEVICE, "read lease: hipEventRecord", e);
+    (void)hipStreamSynchronize(stream);
+    return ::set_err(NW_E_DEVICE, what, e);
   }
   return 0;
+}
+
+int ReadLease::release() {
+  if (!held_) return 0;
+  held_ = false;
+  return reader_release(g_shared[dev_], stream_, "read lease: hipEventRecord");
+}
+
+// The registry's size per device, mirrored for signers_registered(): a verify_batch call with
+// nothing registered must not queue on the device's mutex behind a strict launch's host time or
+// a registration. Written by Lease::signers_set under d.m; the lease decides.
+static std::atomic<uint32_t> g_signers_n[kMaxDevices];
+
+bool signers_registered(int dev_index) {
+  if (dev_index < 0 || dev_index >= kMaxDevices) return false;
+  return g_signers_n[dev_index].load(std::memory_order_acquire) != 0;
+}
+
+// (Lease::signers_set returns with the tables built, so a reader has no event to wait for.)
+int SignersLease::acquire(int dev_index, hipStream_t stream, nw::strict_signers_t* out) {
+  if (held_) return ::set_err(NW_E_INVALID_ARG, "signers lease already held");
+  if (dev_index < 0 || dev_index >= kMaxDevices) return ::set_err(NW_E_INVALID_ARG, "bad device");
+  SharedDev& d = g_shared[dev_index];
+  d.m.lock();
+  if (d.signers.n == 0) {
+    d.m.unlock();
+    return 1;
+  }
+  *out = d.signers;
+  dev_ = dev_index;
+  stream_ = stream;
+  held_ = true;
+  return 0;
+}
+
+int SignersLease::release() {
+  if (!held_) return 0;
+  held_ = false;
+  return reader_release(g_shared[dev_], stream_, "signers lease: hipEventRecord");
 }
 
 int Lease::strict_ws(nw::strict_ws_t* out, size_t n) {
@@ -1238,10 +1276,15 @@ int Lease::strict_ws(nw::strict_ws_t* out, size_t n) {
 int Lease::signers_set(const uint8_t* keys32, size_t n) {
   SharedDev& d = g_shared[dev_];
   // a writer: every queued strict launch on the device is ordered before d.last, and the
-  // holder's stream already waits for it; the old tables are freed only once they are idle
+  // holder's stream already waits for it, and for the verify_batch jobs that read the tables
+  // (SignersLease: the holder's acquire() queued a wait for each reader's event), so the
+  // stream is drained too; the old tables are freed only once they are idle
   if (d.last_valid) (void)hipEventSynchronize(d.last);
+  (void)hipStreamSynchronize(stream_);
+  g_signers_n[dev_] = 0;
   nw::strict_signers_free(&d.signers);
   const hipError_t e = nw::strict_signers_build(keys32, (uint32_t)n, &d.signers, stream_);
+  g_signers_n[dev_].store(d.signers.n, std::memory_order_release);
   if (e == hipSuccess) return 0;
   (void)hipGetLastError();
   if (e == hipErrorOutOfMemory)

@@ -153,6 +153,14 @@ struct batch_skip_t {
 __device__ __forceinline__ bool skipped(const batch_skip_t& sk, uint64_t b) {
   return sk.group_ok && sk.group_ok[b / sk.per_group] != 0;
 }
+// Under a skip list the host sizes the Pippenger grids for every batch of that size, and
+// k_bv_plan_apply lists only those not settled: *pip_count (the plan's device total) of them.
+// A block whose list position is at or past it returns at its top, before it reads the list
+// (uniform over the block: no barrier is left short). pip_count == nullptr: the host's count
+// is the list's.
+__device__ __forceinline__ bool pip_past(const uint32_t* __restrict__ pip_count, uint32_t pos) {
+  return pip_count && pos >= *pip_count;
+}
 
 __device__ __forceinline__ void plan_counts(const uint64_t* offsets, uint64_t b, uint64_t b1,
                                             uint32_t C, uint32_t pmin, const batch_skip_t& sk,
@@ -812,12 +820,12 @@ __device__ __forceinline__ void pip_point_do(
     const uint64_t* __restrict__ offsets, uint64_t b0, uint64_t b1, uint64_t i0, uint64_t i1,
     uint32_t pmin, const uint32_t* __restrict__ pks, const uint32_t* __restrict__ sigs,
     const uint32_t* __restrict__ z16, const z_key_t& zkey, bv_item* __restrict__ items,
-    ge_cached* __restrict__ tabs, const pip_group_t& grp) {
+    ge_cached* __restrict__ tabs, const pip_group_t& grp, const batch_skip_t& sk) {
   const uint64_t gi = i0 + li;
   if (gi >= i1) return;
   const uint64_t lo = batch_of(offsets, b0, b1, gi);
   const uint64_t bs = offsets[lo], n = offsets[lo + 1] - bs;
-  if (n < pmin) return;
+  if (n < pmin || skipped(sk, lo)) return;   // a settled batch is not in pip_list: no region
   const uint64_t t = gi - bs;
   const bool group = grp.cert_vote_offsets != nullptr;
   const uint64_t nreg = n + (group ? grp.nkeys : 0);   // + key sums
@@ -933,10 +941,10 @@ __global__ __launch_bounds__(256, 3) void k_pip_points(
     uint64_t b1, uint64_t i0, uint64_t i1, uint32_t pmin, const uint32_t* __restrict__ pks,
     const uint32_t* __restrict__ sigs, const uint32_t* __restrict__ z16, z_key_t zkey,
     bv_item* __restrict__ items, ge_cached* __restrict__ tabs, pip_group_t grp,
-    uint32_t roles, uint32_t role0) {
+    uint32_t roles, uint32_t role0, batch_skip_t sk) {
   const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, wave = g >> 6;
   pip_point_do((int)(role0 + wave % roles), (wave / roles) * 64 + (g & 63), digests, offsets, b0,
-               b1, i0, i1, pmin, pks, sigs, z16, zkey, items, tabs, grp);
+               b1, i0, i1, pmin, pks, sigs, z16, zkey, items, tabs, grp, sk);
 }
 
 // Group mode: per group, sum_i c_i per committee key (LDS, 64-bit limb sums), reduced mod l,
@@ -1193,10 +1201,12 @@ __global__ __launch_bounds__(1024) void k_pip_sort(const uint32_t* __restrict__ 
                                                    uint64_t b0, uint64_t i0, uint32_t extra,
                                                    uint32_t pmin, ge_cached* __restrict__ tabs,
                                                    const bv_item* __restrict__ items,
-                                                   uint32_t wbase) {
+                                                   uint32_t wbase,
+                                                   const uint32_t* __restrict__ pip_count) {
   __shared__ uint32_t s_h[kPipSortBins], s_c[kPipSortBins];
   __shared__ uint32_t s_b[16][8];
   __shared__ uint32_t s_f[16][4];
+  if (pip_past(pip_count, blockIdx.y)) return;
   const uint64_t bidx = b0 + pip_list[blockIdx.y];
   const uint64_t bs = offsets[bidx], n0 = offsets[bidx + 1] - bs;
   if (n0 < pmin) return;
@@ -1261,7 +1271,8 @@ __global__ __launch_bounds__(256) void k_pip_buckets(const uint32_t* __restrict_
                                                      uint64_t b0, uint64_t i0, uint32_t lg,
                                                      uint32_t npip, uint32_t bpb, int xcd,
                                                      uint32_t extra, uint32_t pmin,
-                                                     ge_cached* __restrict__ tabs) {
+                                                     ge_cached* __restrict__ tabs,
+                                                     const uint32_t* __restrict__ pip_count) {
   uint32_t jb = blockIdx.y, xb = blockIdx.x;
   if (xcd) {
     const uint32_t k = blockIdx.x >> 3;
@@ -1269,6 +1280,7 @@ __global__ __launch_bounds__(256) void k_pip_buckets(const uint32_t* __restrict_
     xb = k % bpb;
     if (jb >= npip) return;
   }
+  if (pip_past(pip_count, jb)) return;
   const uint64_t bidx = b0 + pip_list[jb];
   const uint64_t bs = offsets[bidx], n = offsets[bidx + 1] - bs;
   if (n < pmin) return;
@@ -1286,7 +1298,9 @@ __global__ __launch_bounds__(256) void k_pip_buckets(const uint32_t* __restrict_
 __global__ __launch_bounds__(64) void k_pip_windows(const uint32_t* __restrict__ pip_list,
                                                     const uint64_t* __restrict__ offsets,
                                                     uint64_t b0, uint64_t i0, uint32_t extra,
-                                                    uint32_t pmin, ge_cached* __restrict__ tabs) {
+                                                    uint32_t pmin, ge_cached* __restrict__ tabs,
+                                                    const uint32_t* __restrict__ pip_count) {
+  if (pip_past(pip_count, blockIdx.y)) return;
   const uint64_t bidx = b0 + pip_list[blockIdx.y];
   const uint64_t bs = offsets[bidx], n = offsets[bidx + 1] - bs;
   if (n < pmin) return;
@@ -1534,7 +1548,9 @@ __global__ __launch_bounds__(128) void k_pip_windows_lp(const uint32_t* __restri
                                                        const uint64_t* __restrict__ offsets,
                                                        uint64_t b0, uint64_t i0, uint32_t extra,
                                                        uint32_t pmin,
-                                                       ge_cached* __restrict__ tabs) {
+                                                       ge_cached* __restrict__ tabs,
+                                                       const uint32_t* __restrict__ pip_count) {
+  if (pip_past(pip_count, blockIdx.z)) return;
   const uint64_t bidx = b0 + pip_list[blockIdx.z];
   const uint64_t bs = offsets[bidx], n = offsets[bidx + 1] - bs;
   if (n < pmin) return;
@@ -1555,7 +1571,9 @@ __global__ __launch_bounds__(128) void k_pip_windows_lp(const uint32_t* __restri
 __global__ __launch_bounds__(64) void k_pip_wsum(const uint32_t* __restrict__ pip_list,
                                                  const uint64_t* __restrict__ offsets,
                                                  uint64_t b0, uint64_t i0, uint32_t extra,
-                                                 uint32_t pmin, ge_cached* __restrict__ tabs) {
+                                                 uint32_t pmin, ge_cached* __restrict__ tabs,
+                                                 const uint32_t* __restrict__ pip_count) {
+  if (pip_past(pip_count, blockIdx.y)) return;
   const uint64_t bidx = b0 + pip_list[blockIdx.y];
   const uint64_t bs = offsets[bidx], n = offsets[bidx + 1] - bs;
   if (n < pmin) return;
@@ -1572,8 +1590,10 @@ __global__ __launch_bounds__(64) void k_pip_final(const uint32_t* __restrict__ p
                                                   int32_t* __restrict__ status,
                                                   uint64_t* __restrict__ fail_index,
                                                   uint32_t extra, uint32_t pmin,
-                                                  uint32_t* __restrict__ group_ok) {
+                                                  uint32_t* __restrict__ group_ok,
+                                                  const uint32_t* __restrict__ pip_count) {
   __shared__ uint32_t s_tmp[40];
+  if (pip_past(pip_count, blockIdx.x)) return;
   const uint64_t bidx = b0 + pip_list[blockIdx.x];
   const uint64_t bs = offsets[bidx], n = offsets[bidx + 1] - bs;
   if (n < pmin) return;
@@ -2079,20 +2099,7 @@ __global__ __launch_bounds__(256) void k_key_base(const uint32_t* __restrict__ p
   const bool dec = ge_frombytes(P, Aw, g_bc.k);
   // lambda: [l] A == [lambda] T8 (l A lies in E[8] for every curve point), by
   // double-and-add over the 253 bits of l — once per key per committee
-  uint32_t lam = 0;
-  if (dec && !rows) {
-    ge_cached Pc;
-    ge_to_cached(Pc, P, g_bc.k.d2);
-    ge acc;
-    ge_identity(acc);
-#pragma unroll 1
-    for (int bit = 252; bit >= 0; --bit) {
-      ge_dbl(acc, acc, true);
-      if ((g_bc.l[bit >> 5] >> (bit & 31)) & 1u) ge_add_cached(acc, acc, Pc, true);
-    }
-    const int j = torsion_index(acc, g_bc.tor);
-    lam = j > 0 ? (uint32_t)j : 0u;
-  }
+  const uint32_t lam = dec && !rows ? key_lambda(P, g_bc.l, g_bc.k.d2, g_bc.tor) : 0u;
   ok[i] = (dec ? kKeyDecoded : 0u) | (dec && ge_is_small_order(P) ? kKeySmall : 0u) |
           (lam << kKeyLambdaShift);
   base[2 * i] = P;
@@ -2231,6 +2238,30 @@ hipError_t launch_key_tables_rows(const uint32_t* pks, const uint32_t* rows,
 }
 
 namespace {
+// lam[i] = lambda of key i (nw_strict.hpp key_lambda), 0 for a key that does not decode: one
+// lane per key, once per registration (launch_key_tables_rows leaves lambda out of `ok`).
+__global__ __launch_bounds__(64) void k_key_lambda(const uint32_t* __restrict__ pks, uint64_t nkeys,
+                                                   uint32_t* __restrict__ lam) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nkeys) return;
+  uint32_t Aw[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) Aw[j] = pks[8 * i + j];
+  ge P;
+  const bool dec = ge_frombytes(P, Aw, g_bc.k);
+  lam[i] = dec ? key_lambda(P, g_bc.l, g_bc.k.d2, g_bc.tor) : 0u;
+}
+}  // namespace
+
+hipError_t launch_key_lambda(const uint32_t* pks, uint64_t nkeys, uint32_t* lam,
+                             hipStream_t stream) {
+  if (nkeys == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_key_lambda, dim3((unsigned)((nkeys + 63) / 64)), dim3(64), 0, stream, pks,
+                     nkeys, lam);
+  return hipGetLastError();
+}
+
+namespace {
 
 // ---- config 1's one-call head: the points and the window sorts in ONE launch ------------
 // The sorts read only the digits (role-0 lanes: hash, scalars, recoding), which are done
@@ -2290,7 +2321,7 @@ __global__ __launch_bounds__(256) void k_pip_points_sorted(
     }
     if (grp64 < wv)
       pip_point_do(which, grp64 * 64 + (uint64_t)(tid & 63), digests, offsets, bidx, bidx + 1,
-                   i0, i1, 0, pks, sigs, z16, zkey, items, tabs, nogrp);
+                   i0, i1, 0, pks, sigs, z16, zkey, items, tabs, nogrp, batch_skip_t{nullptr, 1});
     if (t < nb0) {
       // the workgroup's digits, then ONE count (a release per wave is an L2 write-back
       // each: 628 of them slowed the decompressions 73 -> 114 us); the decompressions signal
@@ -2320,21 +2351,26 @@ __global__ __launch_bounds__(256) void k_pip_points_sorted(
 }
 
 // The Pippenger kernels over the pip_list batches of one slice (plain batches or, with
-// grp.cert_vote_offsets set, certificate groups).
+// grp.cert_vote_offsets set, certificate groups). sk / pip_count (plain batches under a skip
+// list, launch_verify_batch's skip_pip): npip and pmax are the host's bounds over every batch of
+// that size, the list holds *pip_count of them, and the fused launches are never taken: they
+// order themselves by tickets and counters, and a block that left early would leave another
+// waiting.
 hipError_t launch_pip(const uint32_t* digests, const uint64_t* offsets, uint64_t b, uint64_t e,
                 uint64_t i0, uint64_t i1, uint32_t pmin, uint64_t npip, uint64_t pmax,
                 const uint32_t* pks, const uint32_t* sigs, const uint32_t* z16,
                 const z_key_t& zkey, const bv_ws& w, int32_t* status, uint64_t* fail_index,
                 const pip_group_t& grp, hipStream_t stream,
                 uint32_t* fctr, const input_gate_t* gate = nullptr, uint32_t* done = nullptr,
-                uint32_t done_seq = 0) {
+                uint32_t done_seq = 0, const batch_skip_t& sk = batch_skip_t{nullptr, 1},
+                const uint32_t* pip_count = nullptr) {
   const bool group = grp.cert_vote_offsets != nullptr;
   const uint32_t extra = group ? grp.nkeys : 0;   // key sums
   const uint32_t roles = group ? 2 : 3;
   const uint64_t wv = (i1 - i0 + 63) / 64;   // waves per role
   // one large batch alone in its slice (config 1's call): the fused head and tail
   const bool fused = pip_fuse_on() && !group && npip == 1 && e - b == 1 && pmax >= kFuseMinN &&
-                     pmax <= kFuseMaxN && npip <= pip_win_lp_max();
+                     pmax <= kFuseMaxN && npip <= pip_win_lp_max() && !pip_count;
   const bool fuse_head = fused && pip_fuse_head_on();
   if (fuse_head) {
     // one large batch alone (config 1's call): points and sorts in one launch
@@ -2350,12 +2386,12 @@ hipError_t launch_pip(const uint32_t* digests, const uint64_t* offsets, uint64_t
   } else {
     hipLaunchKernelGGL(k_pip_points, dim3((unsigned)((wv * roles * 64 + 255) / 256)), dim3(256),
                        0, stream, digests, offsets, b, e, i0, i1, pmin, pks, sigs, z16, zkey,
-                       w.items, w.tabs, grp, roles, 0u);
+                       w.items, w.tabs, grp, roles, 0u, sk);
     if (group)
       hipLaunchKernelGGL(k_grp_keys, dim3((unsigned)npip), dim3(1024), 0, stream, offsets, b,
                          i0, pmin, w.items, w.tabs, grp);
     hipLaunchKernelGGL(k_pip_sort, dim3(kPipWin + 1, (unsigned)npip), dim3(1024), 0, stream,
-                       w.pip_list, offsets, b, i0, extra, pmin, w.tabs, w.items, 0u);
+                       w.pip_list, offsets, b, i0, extra, pmin, w.tabs, w.items, 0u, pip_count);
   }
   // G lanes per bucket: about 8 additions each at the largest batch's mean bucket size
   // (<= 49 digits per vote over kPipBins buckets); more lanes measured slower (the shuffle
@@ -2383,17 +2419,19 @@ hipError_t launch_pip(const uint32_t* digests, const uint64_t* offsets, uint64_t
   const int xcd = npip >= 8;
   const dim3 gb = xcd ? dim3((unsigned)(8 * bpb * ((npip + 7) / 8))) : dim3(bpb, (unsigned)npip);
   hipLaunchKernelGGL(k_pip_buckets, gb, dim3(256), 0, stream, w.pip_list, offsets, b, i0, lg,
-                     (uint32_t)npip, bpb, xcd, extra, pmin, w.tabs);
+                     (uint32_t)npip, bpb, xcd, extra, pmin, w.tabs, pip_count);
   if (npip <= pip_win_lp_max()) {
     hipLaunchKernelGGL(k_pip_windows_lp, dim3(kPipWin + 1, kPipWinLpParts, (unsigned)npip),
-                       dim3(128), 0, stream, w.pip_list, offsets, b, i0, extra, pmin, w.tabs);
+                       dim3(128), 0, stream, w.pip_list, offsets, b, i0, extra, pmin, w.tabs,
+                       pip_count);
     hipLaunchKernelGGL(k_pip_wsum, dim3(kPipWin, (unsigned)npip), dim3(64), 0, stream,
-                       w.pip_list, offsets, b, i0, extra, pmin, w.tabs);
+                       w.pip_list, offsets, b, i0, extra, pmin, w.tabs, pip_count);
   } else
     hipLaunchKernelGGL(k_pip_windows, dim3(kPipWin + 1, (unsigned)npip), dim3(64), 0, stream,
-                       w.pip_list, offsets, b, i0, extra, pmin, w.tabs);
+                       w.pip_list, offsets, b, i0, extra, pmin, w.tabs, pip_count);
   hipLaunchKernelGGL(k_pip_final, dim3((unsigned)npip), dim3(64), 0, stream, w.pip_list,
-                     offsets, b, i0, w.tabs, status, fail_index, extra, pmin, grp.group_ok);
+                     offsets, b, i0, w.tabs, status, fail_index, extra, pmin, grp.group_ok,
+                     pip_count);
   return hipGetLastError();
 }
 
@@ -2435,7 +2473,9 @@ hipError_t launch_verify_batch(const uint32_t* digests, const uint64_t* offsets,
                                const key_tables_t* keys, const uint32_t* skip_group_ok,
                                uint64_t skip_per_group, double active_frac,
                                uint32_t* fuse_ctr, const input_gate_t* gate,
-                               uint32_t* done, uint32_t done_seq) {
+                               uint32_t* done, uint32_t done_seq, bool skip_pip) {
+  // Pippenger batches under a skip list take the separate kernels only (launch_pip)
+  if (skip_pip && (!skip_group_ok || fuse_ctr || gate || done)) return hipErrorInvalidValue;
   // a gate is honoured by the fused head only: refuse it anywhere else (its waves would
   // read bytes the CPU has not written yet)
   if (gate && !verify_batch_gate_ok(nbatches, nitems)) return hipErrorInvalidValue;
@@ -2464,8 +2504,10 @@ hipError_t launch_verify_batch(const uint32_t* digests, const uint64_t* offsets,
   const bool compact = skip_group_ok && frac < 1.0;   // items from the chunk list
   // Batches of at least pmin votes take the Pippenger path (NW_BATCH_PIPPENGER_MIN test
   // hook; never below kPipFloor, whose item slots are the smallest that hold the region).
-  // With a skip list no batch may (launch_cert_groups only skips below pmin).
-  const uint32_t pmin = skip_group_ok ? 0xffffffffu : pip_min();
+  // With a skip list no batch may (launch_cert_groups only skips below pmin), unless the caller
+  // asks for it (skip_pip): the slice then always takes the plan, whose Pippenger list leaves
+  // the settled batches out, and the Pippenger kernels read the plan's device-side count.
+  const uint32_t pmin = skip_group_ok && !skip_pip ? 0xffffffffu : pip_min();
   const pip_group_t nogrp{};
   uint64_t b = 0;
   while (b < nbatches) {
@@ -2491,9 +2533,10 @@ hipError_t launch_verify_batch(const uint32_t* digests, const uint64_t* offsets,
     // the caller's zeroed counters (fused path only, verify_batch_outputs_direct)
     const bool own_ctr = fuse_ctr && nbatches == 1 && pip_fuse_head_on() &&
                          verify_batch_outputs_direct(nbatches, nitems);
+    const uint32_t* const pip_count = skip_pip ? w.plan_tot + 3 * nblk + 2 : nullptr;
     if (npip == e - b && own_ctr) {
       // the fused head and tail read neither the Pippenger list nor zeroed workspace
-    } else if (npip == e - b) {
+    } else if (npip == e - b && !skip_pip) {
       // every batch of the slice takes the Pippenger path (config 1's one 10k batch): no
       // chunk plan, the Pippenger list is the slice's batches in order
       hipLaunchKernelGGL(k_iota, dim3((unsigned)((npip + 255) / 256)), dim3(256), 0, stream,
@@ -2523,7 +2566,7 @@ hipError_t launch_verify_batch(const uint32_t* digests, const uint64_t* offsets,
       const hipError_t pe = launch_pip(digests, offsets, b, e, i0, i1, pmin, npip, pmax, pks,
                                        sigs, z16, zkey, w, status, fail_index, nogrp, stream,
                                        own_ctr ? fuse_ctr : w.chunk_start, gate, done,
-                                       done_seq);
+                                       done_seq, sk, pip_count);
       if (pe != hipSuccess) return pe;
     }
     if (chunks)

@@ -73,6 +73,9 @@ struct nw_job {
     size_t bytes;
   } outs[3];
   int nouts = 0;
+  // verify_batch under the registered signers: the call's four counters in the pinned buffer
+  // (part of its D2H section), added to the process-wide sums when the outputs are delivered
+  const uint64_t* bstats = nullptr;
   bool pending = false;   // device work queued, outputs not yet delivered
   std::vector<nw_job*> parts;   // fan-out parent (dev = -1): one ordinary job per part
   nw::rt::Fork fork{nullptr, nullptr, nullptr};   // certificate jobs: header checks' stream
@@ -94,6 +97,14 @@ struct DevPool {
   std::vector<nw_job*> retiring;
 };
 DevPool g_pool[kMaxDev];
+
+// nw_batch_signers_stats: votes passed, votes not passed, batches settled, batches sent on
+std::atomic<uint64_t> g_bstats[4];
+void job_deliver_bstats(nw_job* j) {
+  if (!j->bstats) return;
+  for (int c = 0; c < 4; ++c) g_bstats[c].fetch_add(j->bstats[c], std::memory_order_relaxed);
+  j->bstats = nullptr;
+}
 
 #define JOB_HIP(call, what)                                      \
   do {                                                           \
@@ -164,6 +175,7 @@ int job_acquire(int dev, nw_job** out) {
   j->early = false;
   j->spin = nullptr;
   j->small_flags = nullptr;
+  j->bstats = nullptr;
   *out = j;
   return 0;
 }
@@ -290,6 +302,7 @@ void job_deliver_early(nw_job* j) {
   std::atomic_thread_fence(std::memory_order_acquire);
   for (int i = 0; i < j->nouts; ++i)
     memcpy(j->outs[i].dst, j->hbuf + j->outs[i].off, j->outs[i].bytes);
+  job_deliver_bstats(j);
   j->nouts = 0;
   j->early = true;
   j->spin = nullptr;
@@ -384,6 +397,7 @@ void job_out(nw_job* j, void* dst, size_t off, size_t bytes) {
 
 void job_deliver(nw_job* j) {
   for (int i = 0; i < j->nouts; ++i) memcpy(j->outs[i].dst, j->hbuf + j->outs[i].off, j->outs[i].bytes);
+  job_deliver_bstats(j);
   j->nouts = 0;
   j->pending = false;
 }
@@ -521,16 +535,39 @@ int submit_batch(int dev, const uint8_t* digests, const uint8_t* pks, const uint
     return 0;
   }
   const size_t m = nitems ? nitems : 1;
+  // Registered signers on the device (DESIGN.md 5 "Round 12"): every vote first takes the comb
+  // check under its registered key, and the batches all of whose votes pass are settled before
+  // launch_verify_batch runs, which then skips them. The path needs the device's B comb; where
+  // that cannot be had (no memory) the call runs as without a registry and no error is left
+  // behind. With nothing registered nothing here adds a launch, an event wait, a copy or a lock
+  // (one atomic load).
+  const nw::ge_niels_pad* bcomb = nullptr;
+  bool signers = nitems != 0 && nw::rt::signers_registered(dev) &&
+                 nitems >= nw::batch_signers_min_votes();
+  if (signers) {
+    // no memory for the table: without the path, as the keyed pipelines fall back
+    // (nw_api.cpp keyed_tables_or_fallback); any other failure is the device's and is reported
+    const hipError_t eb = nw::bcomb_table(&bcomb);
+    if (eb == hipErrorOutOfMemory) {
+      (void)hipGetLastError();
+      signers = false;
+    } else if (eb != hipSuccess) {
+      return job_abort(j, set_err(NW_E_DEVICE, "keyed B comb build", eb));
+    }
+  }
   // a lone batch on the fused path: the launches write the verdict into the pinned buffer
-  // (no copy back) and use the job's own counters (zero between calls)
-  const bool direct = nw::verify_batch_outputs_direct(nbatches, nitems);
+  // (no copy back) and use the job's own counters (zero between calls); never with the comb
+  // phase, whose skip list the fused launches do not read
+  const bool direct = !signers && nw::verify_batch_outputs_direct(nbatches, nitems);
   const size_t o_d = 0, o_off = o_d + a256(32 * nbatches), o_pk = o_off + a256(8 * (nbatches + 1)),
                o_sig = o_pk + a256(32 * m), o_z = o_sig + a256(64 * m),
                o_st = o_z + (z16 ? a256(16 * m) : 0),
                o_fi = o_st + a256(4 * nbatches),
                o_dn = o_fi + a256(8 * nbatches),   // NW_BATCH_SPIN's done word
-               o_ws = o_dn + 256,
-               end = o_ws + a256(nw::batch_workspace_bytes(nbatches, nitems));
+               o_ct = o_dn + 256,                  // the comb phase's four counters
+               o_ws = o_ct + (signers ? 256 : 0),
+               o_sg = o_ws + a256(nw::batch_workspace_bytes(nbatches, nitems)),
+               end = o_sg + (signers ? a256(nw::batch_signers_bytes(nbatches, nitems)) : 0);
   rc = job_reserve(j, o_ws, end);
   if (rc) return job_abort(j, rc);
   // A lone fused batch's inputs go straight from the caller's buffers into host-mapped
@@ -618,6 +655,29 @@ int submit_batch(int dev, const uint8_t* digests, const uint8_t* pks, const uint
     // from here on a gated head may be queued (even if a later launch fails): the votes
     // and their flags are written whatever happens, so no wave is left waiting
     launched = gate;
+    // the comb phase under the registry's read lease, which covers these launches only; a
+    // registry cleared since the look above leaves the counters zero and no skip list
+    const uint32_t* batch_ok = nullptr;
+    if (signers) {
+      unsigned long long* const ctr = reinterpret_cast<unsigned long long*>(j->dbuf + o_ct);
+      nw::rt::SignersLease sl;
+      nw::strict_signers_t sg;
+      const int lrc = sl.acquire(dev, j->stream, &sg);
+      if (lrc < 0) return lrc;
+      if (lrc == 0) {
+        const hipError_t se = nw::launch_batch_signers(
+            reinterpret_cast<const uint32_t*>(ibuf + o_d),
+            reinterpret_cast<const uint64_t*>(ibuf + o_off), nbatches,
+            reinterpret_cast<const uint32_t*>(ibuf + o_pk),
+            reinterpret_cast<const uint32_t*>(ibuf + o_sig), nitems, sg, bcomb, j->dbuf + o_sg,
+            ctr, &batch_ok, j->stream);
+        const int rrc = sl.release();
+        JOB_HIP(se, "verify_batch launch (registered signers)");
+        if (rrc) return rrc;
+      } else {
+        JOB_HIP(hipMemsetAsync(ctr, 0, 32, j->stream), "hipMemsetAsync (signers' counters)");
+      }
+    }
     const hipError_t e = nw::launch_verify_batch(
         reinterpret_cast<const uint32_t*>(ibuf + o_d),
         reinterpret_cast<const uint64_t*>(ibuf + o_off), h_off, nbatches,
@@ -625,8 +685,8 @@ int submit_batch(int dev, const uint8_t* digests, const uint8_t* pks, const uint
         reinterpret_cast<const uint32_t*>(ibuf + o_sig), nitems,
         z16 ? reinterpret_cast<const uint32_t*>(ibuf + o_z) : nullptr, key, j->dbuf + o_ws,
         reinterpret_cast<int32_t*>(obuf + o_st), reinterpret_cast<uint64_t*>(obuf + o_fi),
-        j->stream, nullptr, nullptr, 0, 1.0, out_direct ? j->dfz : nullptr,
-        gate ? &gt : nullptr, done, dseq);
+        j->stream, nullptr, batch_ok, batch_ok ? 1 : 0, 1.0, out_direct ? j->dfz : nullptr,
+        gate ? &gt : nullptr, done, dseq, batch_ok != nullptr);
     if (e != hipSuccess && out_direct) j->dfz_dirty = true;   // the head may have run
     JOB_HIP(e, "verify_batch launch");
     return 0;
@@ -654,6 +714,7 @@ int submit_batch(int dev, const uint8_t* digests, const uint8_t* pks, const uint
   }
   job_out(j, status_out, o_st, 4 * nbatches);
   job_out(j, fail_index_out, o_fi, 8 * nbatches);
+  if (signers) j->bstats = reinterpret_cast<const uint64_t*>(j->hbuf + o_ct);
   if (done) {
     j->spin = reinterpret_cast<volatile uint32_t*>(j->hbuf + o_dn);
     j->spin_seq = dseq;
@@ -1801,6 +1862,14 @@ int nw_job_notify(nw_job* job, void (*fn)(void*), void* arg) {
 }
 
 void nw_job_release(nw_job* job) { job_recycle(job); }
+
+int nw_batch_signers_stats(uint64_t out[4]) {
+  const int rc = nw::rt::ensure_init();
+  if (rc) return rc;
+  if (!out) return set_err(NW_E_INVALID_ARG, "null pointer");
+  for (int c = 0; c < 4; ++c) out[c] = g_bstats[c].load(std::memory_order_relaxed);
+  return 0;
+}
 
 int nw_path_stats(uint64_t* small_jobs, uint64_t* pipeline_jobs) {
   if (small_jobs) *small_jobs = g_small_jobs.load(std::memory_order_relaxed);

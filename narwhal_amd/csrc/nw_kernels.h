@@ -84,12 +84,16 @@ size_t strict_triage_bytes(uint64_t slice, uint64_t key_slots);
 // distinct keys whose 8-bit comb tables (keyspec_for(8), identity rows, no lambda: the layout
 // and flags of a launch's call-local tables) are kept until the set is replaced, in one
 // allocation of their own (base). Their items take the comb check whatever the launch's size;
-// a registered key that does not decode or has small order is never matched.
+// a registered key that does not decode or has small order is never matched. The same tables
+// serve the plain batches (launch_batch_signers), which also need each key's lambda.
 struct strict_signers_t {
   void* base = nullptr;
   const uint32_t* keys = nullptr;    // n x 8 words
   const uint32_t* slots = nullptr;   // cap words: row + 1 or 0
   const uint32_t* ok = nullptr;      // n flag words (kKeyDecoded, kKeySmall)
+  const uint32_t* lam = nullptr;     // n words: lambda with [l]A == [lambda]T8 (0: no torsion
+                                     // component, or the key does not decode); kept out of `ok`,
+                                     // whose words the strict launches read as they are
   const struct ge_niels_pad* tabs = nullptr;
   uint32_t n = 0, cap = 0;
 };
@@ -239,6 +243,9 @@ hipError_t launch_key_tables(const uint32_t* pks, uint64_t nkeys, const keyspec&
 hipError_t launch_key_tables_rows(const uint32_t* pks, const uint32_t* rows,
                                   const uint32_t* nlive, uint64_t ncap, const keyspec& ks,
                                   struct ge_niels_pad* tabs, uint32_t* ok, hipStream_t stream);
+// lam[i] = lambda of key i (nw_strict.hpp key_lambda; 0 when it does not decode), one lane per key.
+hipError_t launch_key_lambda(const uint32_t* pks, uint64_t nkeys, uint32_t* lam,
+                             hipStream_t stream);
 size_t batch_workspace_bytes(uint64_t nbatches, uint64_t nitems);
 // True when launch_verify_batch over these batches (no skip list, no fork) writes its outputs
 // from ONE kernel, the fused tail of a lone large batch: status / fail_index may then be
@@ -266,6 +273,10 @@ bool verify_batch_gate_ok(uint64_t nbatches, uint64_t nitems);
 // skip_group_ok (optional, device): batch b is settled (status Ok) when
 // skip_group_ok[b / skip_per_group] != 0 (launch_cert_groups, launch_votes_keyed);
 // active_frac: the caller's estimate of the fraction of votes not skipped (chunk sizing).
+// skip_pip: with a skip list, batches of Pippenger size still take the Pippenger kernels, which
+// then honour the list (launch_batch_signers' callers); a lone large batch takes the separate
+// kernels, never the fused launches, so fuse_ctr, gate and done must be null. Without it no batch
+// of a call with a skip list takes the Pippenger path (the certificate callers).
 hipError_t launch_verify_batch(const uint32_t* digests, const uint64_t* offsets,
                                const uint64_t* host_offsets, uint64_t nbatches,
                                const uint32_t* pks, const uint32_t* sigs, uint64_t nitems,
@@ -276,7 +287,25 @@ hipError_t launch_verify_batch(const uint32_t* digests, const uint64_t* offsets,
                                uint64_t skip_per_group = 0, double active_frac = 1.0,
                                uint32_t* fuse_ctr = nullptr,
                                const input_gate_t* gate = nullptr,
-                               uint32_t* done = nullptr, uint32_t done_seq = 0);
+                               uint32_t* done = nullptr, uint32_t done_seq = 0,
+                               bool skip_pip = false);
+// Signature::verify_batch under the registered signers (nw_kernels.hip, DESIGN.md 5 "Round 12"):
+// every vote of the call through the comb check under its registered key (sg.n != 0; bcomb: the
+// device's B comb), the parities in batched inversions; *batch_ok_out (in scratch, nbatches words)
+// = 1 for a batch all of whose votes passed, which is then Ok under verify_batch for every
+// coefficient set, 0 otherwise. Follow with launch_verify_batch(skip_group_ok = *batch_ok_out,
+// skip_per_group = 1, skip_pip = true). scratch: batch_signers_bytes(nbatches, nitems) of
+// device memory; counters: 4 device words of 64 bits (set here): votes passed, votes not passed,
+// batches settled, batches sent on. offsets: nbatches + 1 values from 0.
+// batch_signers_min_votes(): the call size from which the path is taken (NW_BATCH_SIGNERS_MIN_VOTES,
+// default 1; NW_BATCH_SIGNERS=0: never), read per call.
+size_t batch_signers_bytes(uint64_t nbatches, uint64_t nitems);
+uint64_t batch_signers_min_votes();
+hipError_t launch_batch_signers(const uint32_t* digests, const uint64_t* offsets, uint64_t nbatches,
+                                const uint32_t* pks, const uint32_t* sigs, uint64_t nitems,
+                                const strict_signers_t& sg, const struct ge_niels_pad* bcomb,
+                                void* scratch, unsigned long long* counters,
+                                const uint32_t** batch_ok_out, hipStream_t stream);
 
 // Certificate::verify vote batches merged over groups of certificates (nw_batch.hip):
 // cert_group_size() = certificates per group, 0 when the merge does not apply;

@@ -701,17 +701,14 @@ __global__ __launch_bounds__(256, NW_COMB_WAVES) void k_strict_keyed_signers(
                     (reg ? rok : keys.ok) + (has ? kk : 0u), bcomb, vp);
 }
 
-// Parity of the pending items (Montgomery's trick per strided chunk, as k_votes_keyed_inv):
-// a match is status 0, a mismatch goes to the list as kVoteDecided (R' = -decode(R): the
-// equation fails whatever else the full verification would look at).
-__global__ __launch_bounds__(256) void k_strict_keyed_inv(uint64_t i0, uint64_t ns,
-                                                          uint64_t nchunks,
-                                                          int32_t* __restrict__ status,
-                                                          vote_planes_t vp,
-                                                          const uint32_t* __restrict__ nlive) {
-  // nlive (optional): nothing to do when *nlive == 0 (k_strict_keyed<true> wrote no state)
-  const uint64_t lane = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (lane >= nchunks || (nlive && *nlive == 0)) return;
+// Parity of the pending items (Montgomery's trick per strided chunk, as k_votes_keyed_inv).
+// keyed_inv_chunk: the chunk of one lane, shared with k_batch_signers_inv; done(i, match)
+// settles pending item i. k_strict_keyed_inv: a match is status 0, a mismatch goes to the list
+// as kVoteDecided (R' = -decode(R): the equation fails whatever else the full verification
+// would look at).
+template <class Done>
+__device__ __forceinline__ void keyed_inv_chunk(uint64_t lane, uint64_t ns, uint64_t nchunks,
+                                                const vote_planes_t& vp, const Done& done) {
   auto load = [&](fe& f, int base, uint64_t i) {
 #pragma unroll
     for (int k = 0; k < 10; ++k) f.v[k] = vp.planes[(uint64_t)(base + k) * vp.S + i];
@@ -742,13 +739,24 @@ __global__ __launch_bounds__(256) void k_strict_keyed_inv(uint64_t i0, uint64_t 
       load(W, 0, i);
       load(Z, 10, i);
       fe_mul(x, W, inv);
-      const bool match = fe_isnegative(x) == (st & 1);
-      if (match) status[i0 + i] = NW_OK;
-      else vp.state[i] = comb_parity_state(false);
+      done(i, fe_isnegative(x) == (st & 1));
       fe_mul(inv, inv, Z);
     }
     if (i < nchunks) break;
   }
+}
+__global__ __launch_bounds__(256) void k_strict_keyed_inv(uint64_t i0, uint64_t ns,
+                                                          uint64_t nchunks,
+                                                          int32_t* __restrict__ status,
+                                                          vote_planes_t vp,
+                                                          const uint32_t* __restrict__ nlive) {
+  // nlive (optional): nothing to do when *nlive == 0 (k_strict_keyed<true> wrote no state)
+  const uint64_t lane = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (lane >= nchunks || (nlive && *nlive == 0)) return;
+  keyed_inv_chunk(lane, ns, nchunks, vp, [&](uint64_t i, bool match) {
+    if (match) status[i0 + i] = NW_OK;
+    else vp.state[i] = comb_parity_state(false);
+  });
 }
 
 // Failed / unkeyed items of the slice -> list (one atomic per wave).
@@ -1056,6 +1064,92 @@ __global__ __launch_bounds__(256) void k_votes_keyed_inv(const uint32_t* __restr
       fe_mul(inv, inv, Z);
     }
     if (i < nchunks) break;
+  }
+}
+
+// ---- plain batches under the registered signers (DESIGN.md 5 "Round 12") ----
+// Signature::verify_batch calls carry no committee, but their signers may be registered
+// (strict_signers_t): every vote of the call takes the comb check under its registered key
+// (nw_strict.hpp batch_signers_vote; k = SHA-512(R || A || digest of its batch)), the parities
+// come from the strided inversion, and batch_ok[b] stays 1 only when every vote of batch b
+// passed. launch_verify_batch then runs with batch_ok as its skip list. No kernel here waits
+// for another block; a failing vote stores a plain 0 (the same value from every failing lane).
+//   k_batch_signers_init   batch_ok[b] = 1 (an empty batch is settled), the four counters = 0
+//   k_batch_signers        one lane per vote
+//   k_batch_signers_inv    parities (keyed_inv_chunk); the state ends as kVotePass / kVoteFail
+//   k_batch_signers_count  votes passed / not passed, batches settled / sent on: block sums,
+//                          one atomic per counter and block
+__device__ __forceinline__ uint64_t vote_batch(const uint64_t* __restrict__ offsets,
+                                               uint64_t nbatches, uint64_t v) {
+  uint64_t lo = 0, hi = nbatches;   // the last b with offsets[b] <= v (empty batches before it)
+  while (hi - lo > 1) {
+    const uint64_t mid = (lo + hi) >> 1;
+    if (offsets[mid] <= v) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+__global__ __launch_bounds__(256) void k_batch_signers_init(uint64_t nbatches,
+                                                            uint32_t* __restrict__ batch_ok,
+                                                            unsigned long long* __restrict__ ctr) {
+  const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < nbatches) batch_ok[b] = 1u;
+  if (b < 4) ctr[b] = 0ull;
+}
+__global__ __launch_bounds__(256, NW_COMB_WAVES) void k_batch_signers(
+    const uint32_t* __restrict__ digests, const uint64_t* __restrict__ offsets, uint64_t nbatches,
+    const uint32_t* __restrict__ pks, const uint32_t* __restrict__ sigs, uint64_t nv,
+    signers_view sv, const uint32_t* __restrict__ rok, const uint32_t* __restrict__ rlam,
+    const ge_niels_pad* __restrict__ rtabs, const ge_niels_pad* __restrict__ bcomb,
+    uint32_t* __restrict__ batch_ok, vote_planes_t vp) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nv) return;
+  const uint64_t b = vote_batch(offsets, nbatches, i);
+  const strict_src_global src{pks + 8 * i, sigs + 16 * i, digests + 8 * b};
+  const keyspec ks = keyspec_for(8);
+  fe X, Z;
+  const uint32_t st = batch_signers_vote(
+      src, g_consts.sk, bcomb_wide{bcomb}, sv, rok, rlam,
+      [&](uint32_t row) { return keytab_wide{rtabs + ks.tab * (uint64_t)row, ks}; }, X, Z);
+  if (st >= kVotePending) {
+#pragma unroll
+    for (int k = 0; k < 10; ++k) {
+      vp.planes[(uint64_t)k * vp.S + i] = X.v[k];
+      vp.planes[(uint64_t)(10 + k) * vp.S + i] = Z.v[k];
+    }
+  }
+  if (st == kVoteFail) batch_ok[b] = 0u;
+  vp.state[i] = st;
+}
+__global__ __launch_bounds__(256) void k_batch_signers_inv(const uint64_t* __restrict__ offsets,
+                                                           uint64_t nbatches, uint64_t nv,
+                                                           uint64_t nchunks,
+                                                           uint32_t* __restrict__ batch_ok,
+                                                           vote_planes_t vp) {
+  const uint64_t lane = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (lane >= nchunks) return;
+  keyed_inv_chunk(lane, nv, nchunks, vp, [&](uint64_t i, bool match) {
+    vp.state[i] = match ? kVotePass : kVoteFail;
+    if (!match) batch_ok[vote_batch(offsets, nbatches, i)] = 0u;
+  });
+}
+__global__ __launch_bounds__(256) void k_batch_signers_count(
+    uint64_t nv, const uint32_t* __restrict__ state, uint64_t nbatches,
+    const uint32_t* __restrict__ batch_ok, unsigned long long* __restrict__ ctr) {
+  __shared__ uint32_t s_sum[4][4];
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool v = i < nv, b = i < nbatches;
+  const bool pass = v && state[i] == kVotePass, okb = b && batch_ok[i] != 0;
+  const bool is[4] = {pass, v && !pass, okb, b && !okb};   // kBsVotesPassed .. kBsSentOn
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const uint32_t n = (uint32_t)__builtin_popcountll(__ballot(is[c]));
+    if ((threadIdx.x & 63u) == 0) s_sum[threadIdx.x >> 6][c] = n;
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    const uint32_t c = threadIdx.x;
+    const uint32_t tot = s_sum[0][c] + s_sum[1][c] + s_sum[2][c] + s_sum[3][c];
+    if (tot) atomicAdd(ctr + c, (unsigned long long)tot);
   }
 }
 
@@ -1529,10 +1623,11 @@ hipError_t strict_signers_build(const uint8_t* keys32, uint32_t n, strict_signer
   memcpy(keys.data(), keys32, 32 * (size_t)n);
   const uint32_t cap = signers_hash_build(keys.data(), n, slots);
   if (cap == 0) return hipErrorInvalidValue;
-  // one allocation: keys | slots | ok | rows | nlive, then the tables (256-byte aligned)
+  // one allocation: keys | slots | ok | rows | nlive | lam, then the tables (256-byte aligned)
   const keyspec ks8 = keyspec_for(8);
   const uint64_t o_slots = 32ull * n, o_ok = o_slots + 4ull * cap, o_rows = o_ok + 4ull * n,
-                 o_live = o_rows + 4ull * n, o_tabs = (o_live + 4 + 255) & ~255ull;
+                 o_live = o_rows + 4ull * n, o_lam = o_live + 4,
+                 o_tabs = (o_lam + 4ull * n + 255) & ~255ull;
   void* base = nullptr;
   hipError_t e = table_malloc(&base, o_tabs + key_tables_bytes(n, ks8));
   if (e != hipSuccess) return e;
@@ -1552,6 +1647,9 @@ hipError_t strict_signers_build(const uint8_t* keys32, uint32_t n, strict_signer
                                reinterpret_cast<const uint32_t*>(b + o_rows),
                                reinterpret_cast<const uint32_t*>(b + o_live), n, ks8, tabs, ok,
                                stream);
+  // each key's torsion image, for the plain batches (launch_batch_signers); `ok` keeps no lambda
+  uint32_t* const lam = reinterpret_cast<uint32_t*>(b + o_lam);
+  if (e == hipSuccess) e = launch_key_lambda(reinterpret_cast<const uint32_t*>(b), n, lam, stream);
   // the uploads read this function's vectors: they must have left before it returns
   const hipError_t e2 = hipStreamSynchronize(stream);
   if (e == hipSuccess) e = e2;
@@ -1563,6 +1661,7 @@ hipError_t strict_signers_build(const uint8_t* keys32, uint32_t n, strict_signer
   out->keys = reinterpret_cast<const uint32_t*>(b);
   out->slots = reinterpret_cast<const uint32_t*>(b + o_slots);
   out->ok = ok;
+  out->lam = lam;
   out->tabs = tabs;
   out->n = n;
   out->cap = cap;
@@ -1850,6 +1949,46 @@ hipError_t launch_votes_keyed(const uint32_t* cert_digest, const uint64_t* cvo, 
     hipLaunchKernelGGL(k_votes_keyed_inv, dim3(grid_for(nchunks, 256)), dim3(256), 0, stream,
                        vote_cert, v0, nv, nchunks, cert_ok, vp);
   }
+  return hipGetLastError();
+}
+
+// Scratch of launch_batch_signers: 20 limb planes and the state word per vote, a word per batch.
+size_t batch_signers_bytes(uint64_t nbatches, uint64_t nitems) {
+  return 4 * (21 * nitems + nbatches);
+}
+uint64_t batch_signers_min_votes() {
+  if (const char* e = getenv("NW_BATCH_SIGNERS"))
+    if (e[0] == '0') return ~0ull;
+  if (const char* e = getenv("NW_BATCH_SIGNERS_MIN_VOTES")) return strtoull(e, nullptr, 10);
+  return 1;
+}
+hipError_t launch_batch_signers(const uint32_t* digests, const uint64_t* offsets, uint64_t nbatches,
+                                const uint32_t* pks, const uint32_t* sigs, uint64_t nitems,
+                                const strict_signers_t& sg, const ge_niels_pad* bcomb,
+                                void* scratch, unsigned long long* counters,
+                                const uint32_t** batch_ok_out, hipStream_t stream) {
+  if (nbatches == 0 || sg.n == 0 || !sg.lam || !bcomb) return hipErrorInvalidValue;
+  uint32_t* const base = static_cast<uint32_t*>(scratch);
+  const vote_planes_t vp{base, base + 20 * nitems, nitems, nullptr};
+  uint32_t* const batch_ok = base + 21 * nitems;
+  hipLaunchKernelGGL(k_batch_signers_init, dim3(grid_for(nbatches, 256)), dim3(256), 0, stream,
+                     nbatches, batch_ok, counters);
+  if (nitems) {
+    hipLaunchKernelGGL(k_batch_signers, dim3(grid_for(nitems, 256)), dim3(256), 0, stream, digests,
+                       offsets, nbatches, pks, sigs, nitems, signers_view{sg.keys, sg.slots, sg.cap},
+                       sg.ok, sg.lam, sg.tabs, bcomb, batch_ok, vp);
+    // chunks: ~2 waves per SIMD of lanes, each over nitems / nchunks votes (>= 1), the sizing of
+    // the strict and certificate-vote launches. Below 131,072 votes that is a lane and an
+    // inversion per pending vote: the lanes are idle otherwise, and chunks of 8 votes measured
+    // slower where latency counts (a lone 10,000-vote call 0.311 against 0.294-0.306 ms, a 34-vote
+    // call 0.257 against 0.240-0.242) and equal on 262,144 votes and above (profiles/r12a)
+    const uint64_t nchunks = std::min<uint64_t>(nitems, 256ull * 4 * 2 * 64);
+    hipLaunchKernelGGL(k_batch_signers_inv, dim3(grid_for(nchunks, 256)), dim3(256), 0, stream,
+                       offsets, nbatches, nitems, nchunks, batch_ok, vp);
+  }
+  hipLaunchKernelGGL(k_batch_signers_count, dim3(grid_for(std::max(nitems, nbatches), 256)),
+                     dim3(256), 0, stream, nitems, vp.state, nbatches, batch_ok, counters);
+  *batch_ok_out = batch_ok;
   return hipGetLastError();
 }
 

@@ -158,5 +158,30 @@ class ReadLease {
   bool held_ = false;
 };
 
+// Read-only use of the registered signers' tables by a verify_batch job (nw_jobs.cpp
+// submit_batch, nw::launch_batch_signers), on the model of ReadLease: readers do not wait for
+// each other, and Lease::signers_set, the only writer, waits for every reader queued before it
+// (their completion events) before it frees the old tables. acquire() returns 0 with the
+// registry, 1 when nothing is registered (nothing is queued, waited for or recorded), or a
+// negative NW_E_*. The device stays locked between acquire() and release(): the host time of the
+// comb-phase launches, which release() closes with the reader's event.
+// signers_registered(): whether the device has any registered signer right now (a hint for
+// sizing a job, one atomic load that takes no lock; the lease decides).
+bool signers_registered(int dev_index);
+class SignersLease {
+ public:
+  SignersLease() = default;
+  SignersLease(const SignersLease&) = delete;
+  SignersLease& operator=(const SignersLease&) = delete;
+  ~SignersLease() { (void)release(); }
+  int acquire(int dev_index, hipStream_t stream, nw::strict_signers_t* out);
+  int release();
+
+ private:
+  int dev_ = -1;
+  hipStream_t stream_ = nullptr;
+  bool held_ = false;
+};
+
 }  // namespace rt
 }  // namespace nw

@@ -75,6 +75,23 @@ NW_HD int torsion_index(const ge& P, const torsion_consts& tc) {
 // weights A by (z k mod l), not z k, so a key with lambda != 0 adds [-(z k div l) lambda] T8
 // to the batch sum even for a vote that passes its strict check.
 constexpr uint32_t kKeyDecoded = 1u, kKeySmall = 2u, kKeyLambdaShift = 2u, kKeyLambdaMask = 0x1cu;
+// lambda of a decoded key A: [l] A by double-and-add over the 253 bits of l (little-endian
+// words; [l] A lies in E[8] for every curve point), named by torsion_index. Once per key per committee (k_key_base) or per
+// registration (k_key_lambda), and the host check's text.
+NW_HD uint32_t key_lambda(const ge& A, const uint32_t l[8], const fe& d2,
+                           const torsion_consts& tc) {
+  ge_cached Pc;
+  ge_to_cached(Pc, A, d2);
+  ge acc;
+  ge_identity(acc);
+#pragma unroll 1
+  for (int bit = 252; bit >= 0; --bit) {
+    ge_dbl(acc, acc, true);
+    if ((l[bit >> 5] >> (bit & 31)) & 1u) ge_add_cached(acc, acc, Pc, true);
+  }
+  const int j = torsion_index(acc, tc);
+  return j > 0 ? (uint32_t)j : 0u;
+}
 
 NW_HD int digit4_of(const uint32_t* w, int nwords, int j) {
   uint32_t word = w[0];
@@ -777,6 +794,31 @@ NW_HD uint32_t keyed_vote_check(const Src& src, const strict_consts& K, const BC
   const uint32_t st = keyed_vote_check_ex(src, K, bc, keytab, keyflags, X, Z, pf);
   return st == kVoteDecided ? kVoteFail : st;
 }
+
+// ---- plain batches under the registered signers (DESIGN.md 5 "Round 12") ----
+// A vote of Signature::verify_batch whose key is registered takes keyed_vote_check under that
+// key's 8-bit tables. Here the flag word carries the key's lambda (the registry keeps it in a
+// word array of its own, so the strict launches' flags stay what they are): a key with a torsion
+// component fails the check, since its term of dalek's sum depends on the coefficients. A vote
+// under no registered key fails too. A batch all of whose votes pass is Ok for every coefficient
+// set; every other batch is decided by the ordinary launch.
+NW_HD uint32_t batch_signers_flags(uint32_t ok, uint32_t lam) {
+  return ok | (lam << kKeyLambdaShift);
+}
+// tab_of(row): the KeyTab of registry row `row`. Returns kVotePass / kVoteFail / kVotePending | sign.
+template <class BComb, class TabOf, class Src>
+NW_HD uint32_t batch_signers_vote(const Src& src, const strict_consts& K, const BComb& bc,
+                                  const signers_view& sv, const uint32_t* ok, const uint32_t* lam,
+                                  const TabOf& tab_of, fe& X, fe& Z) {
+  uint32_t Aw[8];
+  src.A(Aw);
+  const uint32_t row = signers_lookup(sv, Aw);
+  if (row == kNoKey) return kVoteFail;
+  return keyed_vote_check(src, K, bc, tab_of(row), batch_signers_flags(ok[row], lam[row]), X, Z);
+}
+// The four counters of a call (nw_batch_signers_stats), from the votes' final states and the
+// batches' words.
+enum : int { kBsVotesPassed = 0, kBsVotesNot = 1, kBsSettled = 2, kBsSentOn = 3 };
 
 // Keyed strict verification: A is a committee key with comb tables j * 2^(W t) A
 // (keytab_wide / keytab_lazy; affine niels), keyflags bit 0 = decoded, bit 1 = small

@@ -304,24 +304,16 @@ int hc_verify_strict_twopass_scalars(const uint8_t pk[32], const uint8_t sig[64]
 // j * 2^(W t) A computed per lookup (keytab_lazy) by the definition the device's k_key_base /
 // k_key_tabs tabulate, the B comb likewise. Returns the status; -1 when A does not decode is reported through the
 // key flags exactly as the device does (status 3).
+static const torsion_consts& torsion() {
+  static torsion_consts tc;
+  static bool have = false;
+  if (!have) { compute_torsion(tc); have = true; }
+  return tc;
+}
 static uint32_t keyed_key(ge& A, const uint32_t Aw[8]) {
   const bool dec = ge_frombytes(A, Aw, K);
-  uint32_t lam = 0;
-  if (dec) {   // [l] A == [lambda] T8, as k_key_base computes it
-    static torsion_consts tc;
-    static bool have = false;
-    if (!have) { compute_torsion(tc); have = true; }
-    ge_cached Pc;
-    ge_to_cached(Pc, A, K.d2);
-    ge acc;
-    ge_identity(acc);
-    for (int bit = 252; bit >= 0; --bit) {
-      ge_dbl(acc, acc, true);
-      if ((L_W[bit >> 5] >> (bit & 31)) & 1u) ge_add_cached(acc, acc, Pc, true);
-    }
-    const int j = torsion_index(acc, tc);
-    lam = j > 0 ? (uint32_t)j : 0u;
-  }
+  // [l] A == [lambda] T8, the text k_key_base and k_key_lambda run (nw_strict.hpp key_lambda)
+  const uint32_t lam = dec ? key_lambda(A, L_W, K.d2, torsion()) : 0u;
   return (dec ? kKeyDecoded : 0u) | (dec && ge_is_small_order(A) ? kKeySmall : 0u) |
          (lam << kKeyLambdaShift);
 }
@@ -762,6 +754,62 @@ int hc_verify_strict_signers_many(const uint8_t* pks, const uint8_t* sigs, const
   return 0;
 }
 
+// Signature::verify_batch under the registered signers, as launch_batch_signers runs a call
+// (DESIGN.md 5 "Round 12"): the registry of the nreg distinct keys at reg (host-built hash table,
+// the `ok` words of the strict launches, lambda in a word array of its own), every vote through
+// batch_signers_vote (lookup, flags with lambda, keyed_vote_check over the key's lazily computed
+// 8-bit tables; k32 = the vote's SHA-512(R || A || digest of its batch) mod l), a pending vote's
+// parity by one inversion, a failing vote's store into its batch's word, and the four counters.
+// offsets: nbatches + 1 values from 0. settled_out[b] = 1 for a batch all of whose votes passed
+// (an empty one included), lam_out (optional, nreg words) = the registry's lambda array,
+// state_out (optional, one word per vote) = kVotePass / kVoteFail. Returns 0, -3 when no hash
+// table holds the keys.
+int hc_batch_signers_many(const uint8_t* reg, uint32_t nreg, const uint8_t* pks,
+                          const uint8_t* sigs, const uint8_t* k32, const uint64_t* offsets,
+                          uint32_t nbatches, uint32_t* settled_out, uint32_t* lam_out,
+                          uint32_t* state_out, uint64_t stats[4]) {
+  init();
+  std::vector<uint32_t> rkeys(8 * (size_t)nreg), rslots, rok(nreg), rlam(nreg);
+  if (nreg) memcpy(rkeys.data(), reg, 32 * (size_t)nreg);
+  const uint32_t rcap = signers_hash_build(rkeys.data(), nreg, rslots);
+  if (rcap == 0) return -3;
+  const signers_view sv{rkeys.data(), rslots.data(), nreg ? rcap : 0u};
+  std::vector<ge> regA(nreg);
+  for (uint32_t r = 0; r < nreg; ++r) {
+    const bool dec = ge_frombytes(regA[r], rkeys.data() + 8 * (size_t)r, K);
+    rok[r] = (dec ? kKeyDecoded : 0u) | (dec && ge_is_small_order(regA[r]) ? kKeySmall : 0u);
+    rlam[r] = dec ? key_lambda(regA[r], L_W, K.d2, torsion()) : 0u;
+    if (lam_out) lam_out[r] = rlam[r];
+  }
+  const keyspec ks8 = keyspec_for(8);
+  uint64_t ctr[4] = {0, 0, 0, 0};
+  for (uint32_t b = 0; b < nbatches; ++b) settled_out[b] = 1u;
+  for (uint32_t b = 0; b < nbatches; ++b) {
+    for (uint64_t j = offsets[b]; j < offsets[b + 1]; ++j) {
+      uint32_t Aw[8], Rw[8], Sw[8], kw[8];
+      load8(Aw, pks + 32 * j); load8(Rw, sigs + 64 * j);
+      load8(Sw, sigs + 64 * j + 32); load8(kw, k32 + 32 * j);
+      const strict_src_arrays src{Aw, Rw, Sw, kw};
+      fe X, Z;
+      uint32_t st = batch_signers_vote(
+          src, SK, bcomb_lazy{BT, &SK.k.d2}, sv, rok.data(), rlam.data(),
+          [&](uint32_t row) { return keytab_lazy{&regA[row], &SK.k.d2, ks8}; }, X, Z);
+      if (st >= kVotePending) {
+        fe zi, x;
+        fe_invert(zi, Z);
+        fe_mul(x, X, zi);
+        st = fe_isnegative(x) == (st & 1) ? kVotePass : kVoteFail;
+      }
+      if (st != kVotePass) settled_out[b] = 0u;
+      if (state_out) state_out[j] = st;
+      ++ctr[st == kVotePass ? kBsVotesPassed : kBsVotesNot];
+    }
+  }
+  for (uint32_t b = 0; b < nbatches; ++b) ++ctr[settled_out[b] ? kBsSettled : kBsSentOn];
+  if (stats) memcpy(stats, ctr, sizeof(ctr));
+  return 0;
+}
+
 // k's digits at comb width w (key_recode / key_digit): digits[t], t < ntab; returns ntab.
 int hc_key_digits(const uint8_t k32[32], int w, int32_t digits[32]) {
   const keyspec ks = keyspec_for((uint32_t)w);
@@ -813,8 +861,8 @@ int hc_ge_ops(int op, uint32_t n, const uint32_t* A, const uint32_t* B, const in
 // make keysetsan && tools/keyset_san: the key set's sizing and region planning
 // (nw_kernels.h strict_keys_plan / strict_region_plan) and the probe -> build -> triage ->
 // ladder sequence over that region, then the registered signers' hash table (build, lookup,
-// limit) and one slice through a registry, as a stand-alone program under AddressSanitizer /
-// UBSan.
+// limit), one slice through a registry and one verify_batch call under it, as a stand-alone
+// program under AddressSanitizer / UBSan.
 #include <stdio.h>
 #include <vector>
 static int san_fail(const char* what, uint64_t a, uint64_t b) {
@@ -910,6 +958,42 @@ int main() {
       if (on != off) return san_fail("signers: statuses differ", cmin, 0);
       if (ss[0] > 3 || ss[2] > ss[1] || ss[1] > st[1] || st[2] + st[3] != n)
         return san_fail("signers: stats", ss[0], ss[1]);
+    }
+  }
+  // plain batches under the registry (hc_batch_signers_many): empty batches, registered and
+  // unregistered signers, garbage signatures; nothing random passes, every empty batch is settled
+  {
+    const uint32_t nk = 6, nb = 40;
+    std::vector<uint8_t> keys(32 * nk);
+    for (auto& b : keys) b = rnd();
+    std::vector<uint64_t> offs(nb + 1, 0);
+    uint32_t empty = 0;
+    for (uint32_t b = 0; b < nb; ++b) {
+      const uint32_t c = rnd() % 7;
+      empty += c == 0;
+      offs[b + 1] = offs[b] + c;
+    }
+    const uint32_t n = (uint32_t)offs[nb];
+    std::vector<uint8_t> pks(32 * n + 32), sigs(64 * n + 64), ks(32 * n + 32);
+    for (uint32_t j = 0; j < n; ++j) {
+      memcpy(&pks[32 * j], &keys[32 * (j % nk)], 32);
+      for (int t = 0; t < 64; ++t) sigs[64 * j + t] = rnd();
+      sigs[64 * j + 63] &= 0x0f;
+      for (int t = 0; t < 32; ++t) ks[32 * j + t] = rnd();
+      ks[32 * j + 31] &= 0x0f;
+    }
+    for (uint32_t nreg : {0u, 4u, 6u}) {
+      std::vector<uint32_t> settled(nb), lam(nreg), state(n);
+      uint64_t st[4];
+      if (hc_batch_signers_many(keys.data(), nreg, pks.data(), sigs.data(), ks.data(), offs.data(), nb,
+                                settled.data(), lam.data(), state.data(), st))
+        return san_fail("batch signers: run", nreg, 0);
+      if (st[0] != 0 || st[1] != n || st[2] != empty || st[2] + st[3] != nb)
+        return san_fail("batch signers: stats", st[0], st[2]);
+      for (uint32_t b = 0; b < nb; ++b)
+        if (settled[b] != (offs[b + 1] == offs[b] ? 1u : 0u)) return san_fail("batch signers: word", b, settled[b]);
+      for (uint32_t r = 0; r < nreg; ++r)
+        if (lam[r] > 7) return san_fail("batch signers: lambda", r, lam[r]);
     }
   }
   printf("keyset_san ok\n");
