@@ -1207,18 +1207,18 @@ int Lease::strict_ws(nw::strict_ws_t* out, size_t n) {
       return ::set_err(NW_E_OUT_OF_MEMORY, "hipMalloc (strict workspace)", e);
     }
   }
-  // the two-pass path's slice for n items: grown (at least doubled, up to the slice limit's
-  // size) after every queued launch that uses the old one has finished
-  const uint64_t slice = nw::strict_triage_slice(n);
-  // the slice's key set (NW_STRICT_KEYS, read here once per launch): its tables follow the
+  // the launch's plan (its knobs, read here once per launch)
+  nw::strict_launch_plan_t p = nw::strict_launch_plan(n, d.signers.n);
+  // the two-pass path's slice: grown (at least doubled, up to the slice limit's size) after
+  // every queued launch that uses the old one has finished; the key set's tables follow the
   // planes in the same region, which also grows when a launch asks for more slots
-  const uint64_t kslots = n ? nw::strict_keys_slots(slice) : 0;
-  if (n && (slice > d.triage_cap || kslots > d.triage_keys)) {
-    const uint64_t cap = slice > d.triage_cap
-        ? std::max<uint64_t>(slice, std::min<uint64_t>(2 * d.triage_cap,
-                                                       nw::strict_triage_slice(~0ull >> 8)))
+  if (p.slice > d.triage_cap || p.key_slots > d.triage_keys) {
+    const uint64_t cap = p.slice > d.triage_cap
+        ? std::max<uint64_t>(p.slice, std::min<uint64_t>(2 * d.triage_cap,
+                                                         nw::strict_triage_slice(~0ull >> 8)))
         : d.triage_cap;
-    const uint64_t keys = std::max<uint64_t>({kslots, d.triage_keys, nw::strict_keys_slots(cap)});
+    const uint64_t keys =
+        std::max<uint64_t>({p.key_slots, d.triage_keys, nw::strict_keys_slots(cap)});
     if (d.triage_ws) {
       if (d.last_valid) (void)hipEventSynchronize(d.last);
       (void)hipFree(d.triage_ws);
@@ -1234,16 +1234,11 @@ int Lease::strict_ws(nw::strict_ws_t* out, size_t n) {
     d.triage_cap = cap;
     d.triage_keys = keys;
   }
-  // the comb check of the launch's hot keys (NW_STRICT_COMB*, read here once per launch): an
-  // allocation of its own, grown like the region; when it cannot be had the launch runs
-  // without the path
-  const nw::strict_comb_plan_t cp = nw::strict_comb_plan(n ? slice : 0, kslots);
-  // the registered signers: with any, the path is planned even without room for a call-local
-  // table (a slice below NW_STRICT_COMB_MIN), from NW_STRICT_SIGNERS_MIN_ITEMS items on
-  const bool reg = cp.on && d.signers.n != 0 && n >= nw::strict_signers_min_items();
-  if ((cp.hot_cap || reg) && (!d.comb_ws || d.triage_cap > d.comb_slice || d.triage_keys > d.comb_slots ||
-                     cp.hot_cap > d.comb_keys)) {
-    const uint64_t keys = std::max<uint64_t>(cp.hot_cap, d.comb_keys);
+  // the comb path: an allocation of its own, grown like the region; when it cannot be had the
+  // launch runs without the path
+  if (p.comb() && (!d.comb_ws || d.triage_cap > d.comb_slice || d.triage_keys > d.comb_slots ||
+                   p.hot_cap > d.comb_keys)) {
+    const uint64_t keys = std::max<uint64_t>(p.hot_cap, d.comb_keys);
     if (d.comb_ws) {
       if (d.last_valid) (void)hipEventSynchronize(d.last);
       (void)hipFree(d.comb_ws);
@@ -1259,17 +1254,13 @@ int Lease::strict_ws(nw::strict_ws_t* out, size_t n) {
       d.comb_ws = nullptr;
     }
   }
-  out->comb = cp.hot_cap || reg ? d.comb_ws : nullptr;
-  out->comb_keys_cap = d.comb_keys;
-  out->comb_keys = out->comb ? cp.hot_cap : 0;
-  out->comb_min = cp.min;
-  out->signers = out->comb && reg ? d.signers : nw::strict_signers_t{};
-  out->base = d.strict_ws;
-  out->triage = d.triage_ws;
-  out->triage_cap = d.triage_cap;
-  out->key_slots_cap = d.triage_keys;
-  out->slice = n ? slice : 0;
-  out->key_slots = kslots;
+  if (!d.comb_ws) {
+    p.hot_cap = 0;
+    p.signers = false;
+  }
+  *out = nw::strict_ws_t{d.strict_ws, d.triage_ws, p.comb() ? d.comb_ws : nullptr,
+                         {d.triage_cap, d.triage_keys, d.comb_keys}, p,
+                         p.signers ? d.signers : nw::strict_signers_t{}};
   return 0;
 }
 

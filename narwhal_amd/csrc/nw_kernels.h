@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "narwhal_amd.h"
+#include "nw_strict_layout.hpp"
 
 namespace nw {
 
@@ -31,8 +32,9 @@ hipError_t launch_sha512_digest32(const uint8_t* data, const uint64_t* offsets,
 // tables; reusable across launches on one stream).
 size_t strict_workspace_bytes();
 // The two-pass path (unkeyed launches, NW_STRICT_TRIAGE) also needs a region of
-// strict_triage_bytes(slice) for a slice of strict_triage_slice(n) items: per item the x of
-// A and R (20 words), the ladder's digit words, vneg and window count (22) and a list entry.
+// strict_triage_bytes(slice, key_slots) for a slice of strict_triage_slice(n) items: per item
+// the x of A and R (20 words), the ladder's digit words, vneg and window count (22), a list
+// entry and a key slot, then the slice's key set (strict_keys_slots).
 // strict_triage_slice(n) = min(slice limit, n rounded up to 64); the limit is 2^24 items
 // (NW_TRIAGE_SLICE = items lowers it, e.g. to run a small input through several slices);
 // 0 when the two-pass path is off.
@@ -56,29 +58,8 @@ inline uint64_t strict_keys_plan(uint64_t requested, uint64_t slice) {
   return cap;
 }
 uint64_t strict_keys_slots(uint64_t slice);
-// Byte offsets of the region's parts for a slice (a multiple of 64 items) and key_slots slots
-// (0: no key set): kTriagePlaneCount planes, the list and the key-slot plane (a word per item
-// each), a kTriageBlockBytes block (count, nkeys, the diagnostic counters: tabulated keys at
-// byte 8, kKeyStatLanes 64-bit counters of items with a slot from byte 1024, spread so that the
-// blocks of k_strict_keys_probe do not queue on one address), then the key set: slots and flags
-// (a word per slot each), 256 bytes of padding, and the tables (kKeyTabBytes per slot; 256-byte
-// aligned, since every term before them is a multiple of 256).
-constexpr uint64_t kTriagePlaneCount = 42, kKeyTabBytes = 1024, kTriageBlockBytes = 2048;
-constexpr uint32_t kKeyStatLanes = 128;
-struct strict_region_t {
-  uint64_t list, keyslot, block, slots, kflags, ktabs, bytes;
-};
-inline strict_region_t strict_region_plan(uint64_t slice, uint64_t key_slots) {
-  strict_region_t r;
-  r.list = 4 * kTriagePlaneCount * slice;
-  r.keyslot = r.list + 4 * slice;
-  r.block = r.keyslot + 4 * slice;
-  r.slots = r.block + kTriageBlockBytes;
-  r.kflags = r.slots + 4 * key_slots;
-  r.ktabs = r.kflags + 4 * key_slots + 256;
-  r.bytes = r.ktabs + kKeyTabBytes * key_slots;
-  return r;
-}
+// The region for a slice of that many items and key_slots slots (nw_strict_layout.hpp
+// strict_region_plan).
 size_t strict_triage_bytes(uint64_t slice, uint64_t key_slots);
 // The device's registered signers (DESIGN.md 5 "Round 10", nw_strict.hpp signers_lookup): n
 // distinct keys whose 8-bit comb tables (keyspec_for(8), identity rows, no lambda: the layout
@@ -113,19 +94,33 @@ uint64_t strict_signers_min_items();
 // occurred in it (summed over its slices), items checked under them, items the comb passed under
 // them. Synchronises `stream`.
 hipError_t strict_signers_stats(uint64_t out[3], hipStream_t stream);
+// One launch's plan (the knobs, read once per launch: NW_TRIAGE_SLICE, NW_STRICT_KEYS,
+// NW_STRICT_COMB / _MIN / _KEYS, NW_STRICT_SIGNERS_MIN_ITEMS, NW_STRICT_COMB_DECIDE) for n items
+// on a device with `registered` registered signers. n = 0 (a keyed launch), or the two-pass
+// path off: the empty plan.
+struct strict_launch_plan_t {
+  uint64_t slice = 0;        // items per slice (strict_triage_slice(n))
+  uint64_t key_slots = 0;    // strict_keys_slots(slice); 0: no key set
+  uint64_t hot_cap = 0;      // hot keys per slice; 0: no call-local tables
+  uint32_t comb_min = 0;     // uses from which a key is hot
+  bool signers = false;      // the registered signers are used
+  bool comb_decide = true;   // the to-do entries carry the comb's verdict
+  // the comb path runs: with registered signers even without room for a call-local table
+  bool comb() const { return hot_cap != 0 || signers; }
+};
+strict_launch_plan_t strict_launch_plan(uint64_t n, uint32_t registered);
+// What Lease::strict_ws hands a launch: the allocations, what they hold and the launch's plan.
+struct strict_caps_t {
+  uint64_t slice = 0, key_slots = 0;   // triage: strict_triage_bytes(slice, key_slots)
+  uint64_t hot_keys = 0;               // comb: strict_comb_bytes(slice, key_slots, hot_keys)
+};
 struct strict_ws_t {
   void* base = nullptr;       // strict_workspace_bytes()
-  void* triage = nullptr;     // strict_triage_bytes(triage_cap, key_slots_cap), or null (keyed)
-  uint64_t triage_cap = 0;    // items
-  uint64_t key_slots_cap = 0; // slots
-  uint64_t slice = 0;         // strict_triage_slice(n) of the launch this was handed out for
-  uint64_t key_slots = 0;     // strict_keys_slots(slice) of that launch
-  // the comb check of the launch's hot keys (strict_comb_plan; comb == null: off)
-  void* comb = nullptr;       // strict_comb_bytes(triage_cap, key_slots_cap, comb_keys_cap)
-  uint64_t comb_keys_cap = 0; // hot keys the allocation holds
-  uint64_t comb_keys = 0;     // hot_cap of that launch (0: no call-local tables)
-  uint32_t comb_min = 0;      // uses from which a key is hot
-  strict_signers_t signers;   // the device's registered signers for that launch (n == 0: none)
+  void* triage = nullptr;     // null for a keyed launch
+  void* comb = nullptr;       // null: the launch runs without the comb path
+  strict_caps_t caps;
+  strict_launch_plan_t plan;  // without comb: hot_cap = 0 and signers = false
+  strict_signers_t signers;   // the device's registered signers when plan.signers (else n == 0)
 };
 // The comb check for a call's hot keys (DESIGN.md 5 "Round 9"): a key of the slice's set used
 // by at least NW_STRICT_COMB_MIN items (default 256) that decodes and is not small gets 8-bit
@@ -139,14 +134,6 @@ struct strict_ws_t {
 // hot_cap = min(NW_STRICT_COMB_KEYS (default 8192), slice / min). All three are read per
 // launch. The path's allocation (tables, per-slot counts and indices, the to-do list) is
 // apart from the triage region's.
-constexpr uint64_t kCombBlockBytes = 2048;
-constexpr uint32_t kCombStatLanes = 32;
-struct strict_comb_plan_t {
-  uint64_t hot_cap;   // 0: no call-local tables (the path is off, or the slice is below min)
-  uint32_t min;
-  bool on = false;    // NW_STRICT_COMB is not 0 and the launch has a key set
-};
-strict_comb_plan_t strict_comb_plan(uint64_t slice, uint64_t key_slots);
 size_t strict_comb_bytes(uint64_t slice, uint64_t key_slots, uint64_t hot_cap);
 // For the last unkeyed two-pass launch queued on the current device: hot keys tabulated, items
 // checked by the comb, items it passed, items sent on to the triage. Synchronises `stream`.
@@ -185,7 +172,7 @@ hipError_t upload_batch_consts();
 // 13 + 1 tables, 940 MB per key; W = 24 (NW_KEY_WIDTH=24 only): 11 tables.
 // Only these three widths are built for a committee (nw_api.cpp key_width /
 // alloc_key_tables); W = 8 (32 tables of 129 entries, every digit signed, 528 KB per key) is
-// the width of the call-local tables of a strict launch's hot keys (strict_comb_plan) and of
+// the width of the call-local tables of a strict launch's hot keys (strict_launch_plan) and of
 // nothing else. Any other W (e.g. the 0 of a device without tables) is mapped to 16, so that
 // no caller can divide by zero or shift by W - 1 < 0 here, on the host or the device.
 #define NW_KS __host__ __device__ __forceinline__

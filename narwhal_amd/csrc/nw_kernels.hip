@@ -1390,6 +1390,9 @@ hipError_t upload_consts() {
 static inline unsigned grid_for(uint64_t n, unsigned block) {
   return (unsigned)((n + block - 1) / block);
 }
+// Chunks of a batched inversion over n items: ~2 waves per SIMD of lanes, each over
+// n / chunks items (>= 1).
+static inline uint64_t inv_chunks(uint64_t n) { return std::min<uint64_t>(n, 256ull * 4 * 2 * 64); }
 
 hipError_t launch_sha512_digest32(const uint8_t* data, const uint64_t* offsets,
                                   const uint64_t* lengths, uint64_t n, uint32_t* out,
@@ -1425,18 +1428,19 @@ static unsigned strict_grid() {
 constexpr uint64_t kKeyedSliceMax = 1ull << 22;
 // (sized for 160-byte entries; the packed ones use 128 of each 160)
 static size_t strict_tabs_bytes() { return (size_t)strict_grid() * 256 * 16 * sizeof(ge_cached); }
+static bool env_is_zero(const char* name) {
+  const char* e = getenv(name);
+  return e && e[0] == '0';
+}
 bool strict_triage_on() {   // NW_STRICT_TRIAGE=0: one pass (k_verify_strict), A/B hook
-  static const bool v = [] {
-    const char* e = getenv("NW_STRICT_TRIAGE");
-    return !(e && e[0] == '0');
-  }();
+  static const bool v = !env_is_zero("NW_STRICT_TRIAGE");
   return v;
 }
 static size_t strict_keyed_region_bytes() { return 4 * kKeyedSliceMax + 256; }
 size_t strict_workspace_bytes() { return strict_tabs_bytes() + strict_keyed_region_bytes(); }
 // The two-pass path's slice (k_strict_triage / k_verify_strict_pre): kTriagePlanes words and
-// a list entry and a key slot per item, then the count and the key set (nw_kernels.h
-// strict_region_plan); a region of its own, sized for the launch (176 B per item and 1 KB
+// a list entry and a key slot per item, then the block and the key set
+// (nw_strict_layout.hpp strict_region_plan); a region of its own, sized for the launch (176 B per item and 1 KB
 // per key slot: 3.0 GB at the limit, 2.3 GB for config 4's 12.5M items). The limit is
 // large: config 4 is one slice, so the second pass's last, partly filled round over the
 // resident lanes comes once per launch.
@@ -1468,135 +1472,116 @@ size_t strict_triage_bytes(uint64_t slice, uint64_t key_slots) {
   return strict_region_plan(slice, key_slots).bytes;
 }
 
-// The comb path's plan for a launch (nw_kernels.h): the three knobs, read per launch.
-strict_comb_plan_t strict_comb_plan(uint64_t slice, uint64_t key_slots) {
-  strict_comb_plan_t p{0, 256};
-  if (const char* e = getenv("NW_STRICT_COMB"))
-    if (e[0] == '0') return p;
-  if (slice == 0 || key_slots == 0) return p;
-  p.on = true;
+// The comb path's region (nw_strict_layout.hpp) with the 8-bit tables of hot_cap keys.
+static comb_region_t comb_plan(uint64_t slice, uint64_t key_slots, uint64_t hot_cap) {
+  return comb_region_plan(slice, key_slots, hot_cap, key_tables_bytes(hot_cap, keyspec_for(8)));
+}
+size_t strict_comb_bytes(uint64_t slice, uint64_t key_slots, uint64_t hot_cap) {
+  return comb_plan(slice, key_slots, hot_cap).bytes;
+}
+
+strict_launch_plan_t strict_launch_plan(uint64_t n, uint32_t registered) {
+  strict_launch_plan_t p;
+  if (n == 0 || (p.slice = strict_triage_slice(n)) == 0) return p;
+  p.key_slots = strict_keys_slots(p.slice);
+  // NW_STRICT_COMB_DECIDE=0: the comb path's to-do entries carry no verdict, so every listed
+  // item that survives the triage takes the ladder (rounds 9-10's sequence; A/B hook)
+  p.comb_decide = !env_is_zero("NW_STRICT_COMB_DECIDE");
+  p.comb_min = 256;
+  if (p.key_slots == 0 || env_is_zero("NW_STRICT_COMB")) return p;
   if (const char* e = getenv("NW_STRICT_COMB_MIN")) {
     const unsigned long long v = strtoull(e, nullptr, 10);
-    p.min = (uint32_t)std::min<unsigned long long>(std::max<unsigned long long>(v, 1), 1u << 30);
+    p.comb_min = (uint32_t)std::min<unsigned long long>(std::max<unsigned long long>(v, 1), 1u << 30);
   }
   uint64_t keys = 8192;
   if (const char* e = getenv("NW_STRICT_COMB_KEYS")) keys = strtoull(e, nullptr, 10);
-  p.hot_cap = std::min<uint64_t>({keys, slice / p.min, 1ull << 20});
+  p.hot_cap = std::min<uint64_t>({keys, p.slice / p.comb_min, 1ull << 20});
+  p.signers = registered != 0 && n >= strict_signers_min_items();
   return p;
 }
-// The path's allocation: a kCombBlockBytes block (the slice's words: nhot, the to-do count and
-// nlive = hot keys + registered keys in the slice, kCombSliceBytes in all; then the launch's
-// counters, 64 bits each: hot keys, items checked, items listed from kCombStatsAt, registered
-// keys matched and items handed to the ladder after them, and from kCombLanesAt 3 x
-// kCombStatLanes of k_strict_signers_count and kCombStatLanes of the triage's settled items),
-// the to-do list (a word per item of the slice), per slot of the key
-// set its uses, its hot index and its registry row, per hot key its owner's row and its flags,
-// then the tables (key_tables_bytes).
-namespace {
-constexpr uint64_t kCombSliceBytes = 16, kCombStatsAt = 16, kCombLanesAt = 1024;
-static_assert(kCombStatsAt + 8 * 5 <= kCombLanesAt &&
-                  kCombLanesAt + 8 * 4 * kCombStatLanes <= kCombBlockBytes,
-              "the block's counters");
-struct comb_region_t {
-  uint64_t todo, uses, hotidx, match, hotrow, hok, tabs, bytes;
-};
-comb_region_t comb_region_plan(uint64_t slice, uint64_t key_slots, uint64_t hot_cap) {
-  comb_region_t r;
-  r.todo = kCombBlockBytes;
-  r.uses = r.todo + 4 * slice;
-  r.hotidx = r.uses + 4 * key_slots;
-  r.match = r.hotidx + 4 * key_slots;
-  r.hotrow = r.match + 4 * key_slots;
-  r.hok = r.hotrow + 4 * hot_cap;
-  r.tabs = (r.hok + 4 * hot_cap + 255) & ~255ull;
-  r.bytes = r.tabs + key_tables_bytes(hot_cap, keyspec_for(8));
-  return r;
-}
-}  // namespace
-size_t strict_comb_bytes(uint64_t slice, uint64_t key_slots, uint64_t hot_cap) {
-  return comb_region_plan(slice, key_slots, hot_cap).bytes;
-}
 
-// Diagnostics of the last unkeyed two-pass launch per device (strict_keyset_stats,
-// strict_comb_stats).
+// ---- diagnostics: the counters of the last unkeyed two-pass launch per device ----
 namespace {
-struct keyset_record_t {
-  const char* dev = nullptr;   // the region's block (strict_region_plan)
+struct two_pass_record_t {
+  const triage_block_t* triage = nullptr;   // counted only with a key set (keys_on)
+  const comb_block_t* comb = nullptr;       // null: the comb path was off
   uint64_t n = 0;
-  bool valid = false, on = false;
-  const char* comb = nullptr;  // the comb path's block, or null: the path was off
+  bool valid = false, keys_on = false;
 };
-std::mutex g_keyset_m;
-keyset_record_t g_keyset_last[64];
-}  // namespace
-hipError_t strict_comb_stats(uint64_t out[4], hipStream_t stream) {
+std::mutex g_two_pass_m;
+two_pass_record_t g_two_pass_last[64];
+struct strict_counters_t {
+  two_pass_record_t rec;   // !valid: no launch yet, nothing was read
+  triage_block_t triage;   // read when rec.keys_on
+  comb_block_t comb;       // read when rec.comb
+};
+// Synchronises `stream`, then copies the blocks that the launch counted in.
+hipError_t strict_last_counters(hipStream_t stream, strict_counters_t* s) {
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return e;
-  keyset_record_t rec;
   {
-    std::lock_guard<std::mutex> g(g_keyset_m);
-    if (dev >= 0 && dev < 64) rec = g_keyset_last[dev];
+    std::lock_guard<std::mutex> g(g_two_pass_m);
+    s->rec = dev >= 0 && dev < 64 ? g_two_pass_last[dev] : two_pass_record_t{};
   }
-  out[0] = out[1] = out[2] = out[3] = 0;
-  if (!rec.valid) return hipSuccess;
+  if (!s->rec.valid) return hipSuccess;
   e = hipStreamSynchronize(stream);
-  if (e != hipSuccess) return e;
-  out[3] = rec.n;
-  if (!rec.comb) return hipSuccess;
-  std::vector<unsigned long long> h(kCombBlockBytes / 8);
-  e = hipMemcpy(h.data(), rec.comb, kCombBlockBytes, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return e;
-  const unsigned long long* c = h.data() + kCombStatsAt / 8;
-  out[0] = c[0];
-  out[1] = c[1];   // k_strict_keyed<true>'s count, or k_strict_signers_count's lanes
-  for (uint32_t t = 0; t < kCombStatLanes; ++t) out[1] += h[kCombLanesAt / 8 + t];
-  out[3] = c[2];
-  out[2] = rec.n - c[2];   // every item is either passed by the comb or listed
+  if (e == hipSuccess && s->rec.keys_on)
+    e = hipMemcpy(&s->triage, s->rec.triage, sizeof(s->triage), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && s->rec.comb)
+    e = hipMemcpy(&s->comb, s->rec.comb, sizeof(s->comb), hipMemcpyDeviceToHost);
+  return e;
+}
+template <size_t N>
+uint64_t lane_sum(const unsigned long long (&lanes)[N]) {
+  uint64_t t = 0;
+  for (unsigned long long v : lanes) t += v;
+  return t;
+}
+}  // namespace
+hipError_t strict_keyset_stats(uint64_t out[3], hipStream_t stream) {
+  strict_counters_t s;
+  out[0] = out[1] = out[2] = 0;
+  const hipError_t e = strict_last_counters(stream, &s);
+  if (e != hipSuccess || !s.rec.valid) return e;
+  if (s.rec.keys_on) {
+    out[0] = s.triage.keys_tabulated;
+    out[1] = lane_sum(s.triage.with_slot);
+  }
+  out[2] = s.rec.n - out[1];
+  return hipSuccess;
+}
+hipError_t strict_comb_stats(uint64_t out[4], hipStream_t stream) {
+  strict_counters_t s;
+  out[0] = out[1] = out[2] = out[3] = 0;
+  const hipError_t e = strict_last_counters(stream, &s);
+  if (e != hipSuccess || !s.rec.valid) return e;
+  out[3] = s.rec.n;
+  if (!s.rec.comb) return hipSuccess;
+  out[0] = s.comb.hot_keys;
+  // k_strict_keyed<true>'s count, or k_strict_signers_count's lanes
+  out[1] = s.comb.checked + lane_sum(s.comb.lane_checked);
+  out[2] = s.rec.n - s.comb.listed;   // every item is either passed by the comb or listed
+  out[3] = s.comb.listed;
   return hipSuccess;
 }
 hipError_t strict_decided_stats(uint64_t out[2], hipStream_t stream) {
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  keyset_record_t rec;
-  {
-    std::lock_guard<std::mutex> g(g_keyset_m);
-    if (dev >= 0 && dev < 64) rec = g_keyset_last[dev];
-  }
+  strict_counters_t s;
   out[0] = out[1] = 0;
-  if (!rec.valid) return hipSuccess;
-  e = hipStreamSynchronize(stream);
-  if (e != hipSuccess || !rec.comb) return e;
-  std::vector<unsigned long long> h(kCombBlockBytes / 8);
-  e = hipMemcpy(h.data(), rec.comb, kCombBlockBytes, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return e;
-  for (uint32_t t = 0; t < kCombStatLanes; ++t)
-    out[0] += h[kCombLanesAt / 8 + 3 * kCombStatLanes + t];
-  out[1] = h[kCombStatsAt / 8 + 4];
+  const hipError_t e = strict_last_counters(stream, &s);
+  if (e != hipSuccess || !s.rec.valid || !s.rec.comb) return e;
+  out[0] = lane_sum(s.comb.lane_settled);
+  out[1] = s.comb.laddered;
   return hipSuccess;
 }
 hipError_t strict_signers_stats(uint64_t out[3], hipStream_t stream) {
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  keyset_record_t rec;
-  {
-    std::lock_guard<std::mutex> g(g_keyset_m);
-    if (dev >= 0 && dev < 64) rec = g_keyset_last[dev];
-  }
+  strict_counters_t s;
   out[0] = out[1] = out[2] = 0;
-  if (!rec.valid) return hipSuccess;
-  e = hipStreamSynchronize(stream);
-  if (e != hipSuccess || !rec.comb) return e;
-  std::vector<unsigned long long> h(kCombBlockBytes / 8);
-  e = hipMemcpy(h.data(), rec.comb, kCombBlockBytes, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return e;
-  out[0] = h[kCombStatsAt / 8 + 3];
-  for (uint32_t t = 0; t < kCombStatLanes; ++t) {
-    out[1] += h[kCombLanesAt / 8 + kCombStatLanes + t];
-    out[2] += h[kCombLanesAt / 8 + 2 * kCombStatLanes + t];
-  }
+  const hipError_t e = strict_last_counters(stream, &s);
+  if (e != hipSuccess || !s.rec.valid || !s.rec.comb) return e;
+  out[0] = s.comb.matched;
+  out[1] = lane_sum(s.comb.lane_reg_items);
+  out[2] = lane_sum(s.comb.lane_reg_passed);
   return hipSuccess;
 }
 
@@ -1667,232 +1652,228 @@ hipError_t strict_signers_build(const uint8_t* keys32, uint32_t n, strict_signer
   out->cap = cap;
   return hipSuccess;
 }
-hipError_t strict_keyset_stats(uint64_t out[3], hipStream_t stream) {
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  keyset_record_t rec;
-  {
-    std::lock_guard<std::mutex> g(g_keyset_m);
-    if (dev >= 0 && dev < 64) rec = g_keyset_last[dev];
+// ---- launch_verify_strict: the two-pass launch, the one-pass launch, the keyed fast path ----
+namespace {
+struct strict_items_t {   // what a launch verifies, and where its verdicts go
+  const uint32_t* msgs;
+  uint32_t msg_stride_words;
+  const uint32_t *pks, *sigs;
+  uint64_t n;
+  int32_t* status;
+  uint64_t* bitmap;
+  hipStream_t stream;
+};
+// k_strict_todo_list and k_strict_signers_count: a block takes kTodoPer x 256 consecutive items
+unsigned todo_grid(uint64_t ns) { return grid_for(ns, 256 * kTodoPer); }
+
+// The launch's plan against what the allocations hold (Lease::strict_ws makes both).
+bool strict_plan_fits(const strict_ws_t& ws, bool comb_on) {
+  const strict_launch_plan_t& p = ws.plan;
+  const strict_caps_t& c = ws.caps;
+  if (!ws.triage || p.slice == 0 || c.slice < p.slice || p.key_slots > c.key_slots) return false;
+  if (strict_triage_bytes(p.slice, p.key_slots) > strict_triage_bytes(c.slice, c.key_slots))
+    return false;
+  return !comb_on || (p.comb_min != 0 && strict_comb_bytes(p.slice, p.key_slots, p.hot_cap) <=
+                                             strict_comb_bytes(c.slice, c.key_slots, c.hot_keys));
+}
+
+// One slice (items i0 .. i0 + ns) of the two-pass launch. cv is empty without the comb path.
+hipError_t strict_two_pass_slice(const strict_items_t& in, const strict_ws_t& ws,
+                                 const strict_region_view& tv, const comb_region_view& cv,
+                                 const ge_niels_pad* btw, const ge_niels_pad* bcomb, uint64_t i0,
+                                 uint64_t ns) {
+  const strict_signers_t& sg = ws.signers;
+  const uint64_t slice = ws.plan.slice;
+  const uint32_t kcap = (uint32_t)ws.plan.key_slots, hot_cap = (uint32_t)ws.plan.hot_cap;
+  hipStream_t const stream = in.stream;
+  const dim3 lanes(256), per_item(grid_for(ns, 256)), per_slot(grid_for(kcap, 256));
+  triage_block_t* const tb = tv.block;
+  // the comb path's words that the triage and the ladder read and count in (null without it).
+  // live: the word by which the slice's comb kernels, the to-do list and the triage see that the
+  // slice has nothing for the comb: hot keys + registered keys with registered signers, hot
+  // keys without them
+  comb_block_t* const cb = cv.block;
+  const bool reg_on = cb && sg.n != 0;
+  uint32_t *todo_count = nullptr, *live = nullptr;
+  unsigned long long *listed = nullptr, *settled = nullptr, *laddered = nullptr;
+  if (cb) {
+    todo_count = &cb->todo_count;
+    live = reg_on ? &cb->nlive : &cb->nhot;
+    listed = &cb->listed;
+    settled = cb->lane_settled;
+    laddered = &cb->laddered;
   }
-  out[0] = out[1] = out[2] = 0;
-  if (!rec.valid) return hipSuccess;
-  e = hipStreamSynchronize(stream);
+  hipError_t e = hipMemsetAsync(tb, 0, kTriageSliceWordsBytes, stream);
   if (e != hipSuccess) return e;
-  if (!rec.on) {
-    out[2] = rec.n;
-    return hipSuccess;
+  if (kcap) {
+    // the slice's key set: each key's slot, then each slot's flags and table, once
+    e = hipMemsetAsync(tv.slots, 0, 4 * (size_t)kcap, stream);
+    if (e == hipSuccess && cb) e = hipMemsetAsync(cb, 0, kCombSliceWordsBytes, stream);
+    if (e == hipSuccess && cb) e = hipMemsetAsync(cv.uses, 0, 4 * (size_t)kcap, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_strict_keys_probe, per_item, lanes, 0, stream, in.pks, i0, ns, tv.slots,
+                       kcap, kcap / 2, &tb->nkeys, tv.keyslot, tb->with_slot, cv.uses);
+    hipLaunchKernelGGL(k_strict_keys_build, per_slot, lanes, 0, stream, in.pks, i0, tv.slots, kcap,
+                       tv.kflags, tv.ktabs, &tb->keys_tabulated);
   }
-  static_assert(1024 + 8 * kKeyStatLanes <= kTriageBlockBytes, "the block's counters");
-  std::vector<unsigned long long> h(kTriageBlockBytes / 8);
-  e = hipMemcpy(h.data(), rec.dev, kTriageBlockBytes, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return e;
-  out[0] = h[1];
-  for (uint32_t t = 0; t < kKeyStatLanes; ++t) out[1] += h[128 + t];
-  out[2] = rec.n - out[1];
+  if (cb) {
+    // the slice's hot keys and their 8-bit comb tables, then the comb check of their items:
+    // a pass is status 0 (k_strict_keyed, or k_strict_keyed_inv for the x parity); every
+    // other item of the slice goes on the to-do list, with the comb's verdict in the entry
+    // when its sum ran (the triage then settles the item without the ladder). X' / Z' and the
+    // state use the region's planes 0-20, which the triage overwrites afterwards.
+    if (reg_on)
+      hipLaunchKernelGGL(k_strict_signers_match, per_slot, lanes, 0, stream, in.pks, i0, tv.slots,
+                         kcap, tv.kflags, signers_view{sg.keys, sg.slots, sg.cap}, cv.match,
+                         &cb->nlive, &cb->matched);
+    hipLaunchKernelGGL(k_strict_comb_select, per_slot, lanes, 0, stream, tv.slots, kcap, tv.kflags,
+                       cv.uses, ws.plan.comb_min, hot_cap, &cb->nhot, cv.hotidx, cv.hotrow,
+                       &cb->hot_keys, reg_on ? cv.match : nullptr, reg_on ? sg.n : 0u,
+                       reg_on ? &cb->nlive : nullptr);
+    const keyspec ks8 = keyspec_for(8);
+    e = launch_key_tables_rows(in.pks + 8 * i0, cv.hotrow, &cb->nhot, hot_cap, ks8, cv.tabs, cv.hok,
+                               stream);
+    if (e != hipSuccess) return e;
+    const vote_planes_t vp{tv.planes, tv.planes + 20 * slice, slice, nullptr};
+    const key_tables_t hk{cv.tabs, cv.hok, tv.keyslot, ks8};
+    if (reg_on)
+      hipLaunchKernelGGL(k_strict_keyed_signers, per_item, lanes, 0, stream, in.msgs,
+                         in.msg_stride_words, in.pks, in.sigs, i0, ns, in.status, hk, bcomb, vp,
+                         cv.hotidx, &cb->nhot, &cb->nlive, sg.tabs, sg.ok, sg.n);
+    else
+      hipLaunchKernelGGL(k_strict_keyed<true>, per_item, lanes, 0, stream, in.msgs,
+                         in.msg_stride_words, in.pks, in.sigs, i0, ns, in.status, hk, bcomb, vp, 0,
+                         cv.hotidx, &cb->nhot, &cb->checked);
+    const uint64_t nchunks = inv_chunks(ns);
+    hipLaunchKernelGGL(k_strict_keyed_inv, dim3(grid_for(nchunks, 256)), lanes, 0, stream, i0, ns,
+                       nchunks, in.status, vp, live);
+    if (reg_on)
+      hipLaunchKernelGGL(k_strict_signers_count, dim3(todo_grid(ns)), lanes, 0, stream, ns,
+                         tv.keyslot, cv.hotidx, &cb->nhot, &cb->nlive, sg.n, vp.state,
+                         cb->lane_checked);
+    hipLaunchKernelGGL(k_strict_todo_list, dim3(todo_grid(ns)), lanes, 0, stream, ns, vp.state,
+                       cv.todo, todo_count, live, (uint32_t)ws.plan.comb_decide);
+  }
+  hipLaunchKernelGGL(k_strict_triage, per_item, lanes, 0, stream, in.msgs, in.msg_stride_words,
+                     in.pks, in.sigs, i0, ns, in.status, tv.planes, slice, tv.list, &tb->count,
+                     tv.keyslot, tv.kflags, cv.todo, todo_count, listed, live, settled);
+  hipLaunchKernelGGL(k_verify_strict_pre, dim3(std::min<uint64_t>(strict_grid(), per_item.x)),
+                     lanes, 0, stream, in.msgs, in.msg_stride_words, in.pks, in.sigs, i0, tv.list,
+                     &tb->count, tv.planes, slice, in.status, static_cast<ge_cached_pk*>(ws.base),
+                     btw, tv.ktabs, laddered);
   return hipSuccess;
 }
 
-hipError_t launch_verify_strict(const uint32_t* msgs, uint32_t msg_stride_words,
-                                const uint32_t* pks, const uint32_t* sigs, uint64_t n,
-                                int32_t* status, uint64_t* bitmap, const strict_ws_t& wsp,
-                                hipStream_t stream, const key_tables_t* keys) {
-  if (n == 0) return hipSuccess;
-  void* const workspace = wsp.base;
-  const unsigned grid = std::min<uint64_t>(strict_grid(), grid_for(n, 256));
-  const key_tables_t kt = keys ? *keys : key_tables_t{nullptr, nullptr, nullptr, {}};
-  const ge_niels_pad* btw = nullptr;
-  const ge_niels_pad* bcomb = nullptr;
-  hipError_t eb = btab_for_current_device(0, &btw);
-  if (eb == hipSuccess && kt.vote_key) eb = btab_for_current_device(1, &bcomb);
-  if (eb != hipSuccess) return eb;
-  const char* kf = getenv("NW_STRICT_KEYED_FAST");
-  // NW_STRICT_COMB_DECIDE=0: the comb path's to-do entries carry no verdict, so every listed
-  // item that survives the triage takes the ladder (rounds 9-10's sequence; A/B hook)
-  const char* cd = getenv("NW_STRICT_COMB_DECIDE");
-  const uint32_t comb_decide = !(cd && cd[0] == '0');
-  // the comb check of the call's hot keys needs its allocation (Lease::strict_ws) and the B
+// The unkeyed launch in two passes (NW_STRICT_TRIAGE), slice by slice.
+hipError_t launch_strict_two_pass(const strict_items_t& in, const strict_ws_t& ws,
+                                  const ge_niels_pad* btw) {
+  const strict_launch_plan_t& p = ws.plan;
+  // the comb check needs its allocation (Lease::strict_ws plans none without one) and the B
   // comb; without either the launch runs without it
-  // (with registered signers the path runs even without room for call-local tables)
-  const strict_signers_t& sg = wsp.signers;
-  bool comb_on = !kt.vote_key && strict_triage_on() && wsp.comb && (wsp.comb_keys || sg.n) &&
-                 wsp.key_slots;
-  if (comb_on && btab_for_current_device(1, &bcomb) != hipSuccess) {
-    comb_on = false;
-    bcomb = nullptr;
+  const ge_niels_pad* bcomb = nullptr;
+  const bool comb_on = ws.comb && p.comb() && p.key_slots &&
+                       btab_for_current_device(1, &bcomb) == hipSuccess;
+  if (!comb_on) bcomb = nullptr;
+  if (!strict_plan_fits(ws, comb_on)) return hipErrorInvalidValue;
+  const strict_region_view tv(ws.triage, strict_region_plan(p.slice, p.key_slots),
+                              p.key_slots != 0);
+  const comb_region_view cv =
+      comb_on ? comb_region_view(ws.comb, comb_plan(p.slice, p.key_slots, p.hot_cap))
+              : comb_region_view();
+  // the launch's counters, kept over its slices
+  hipError_t e = hipSuccess;
+  if (p.key_slots)
+    e = hipMemsetAsync(&tv.block->keys_tabulated, 0,
+                       sizeof(triage_block_t) - kTriageSliceWordsBytes, in.stream);
+  if (e == hipSuccess && cv.block)
+    e = hipMemsetAsync(&cv.block->hot_keys, 0, sizeof(comb_block_t) - kCombSliceWordsBytes,
+                       in.stream);
+  if (e != hipSuccess) return e;
+  int dev = 0;
+  if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
+    std::lock_guard<std::mutex> g(g_two_pass_m);
+    g_two_pass_last[dev] = two_pass_record_t{tv.block, cv.block, in.n, true, p.key_slots != 0};
   }
-  if (!kt.vote_key && strict_triage_on()) {
-    // the slice Lease::strict_ws chose for this launch (one read of NW_TRIAGE_SLICE per launch)
-    const uint64_t slice = wsp.slice;
-    if (!wsp.triage || slice == 0 || wsp.triage_cap < slice) return hipErrorInvalidValue;
-    if (wsp.key_slots > wsp.key_slots_cap) return hipErrorInvalidValue;
-    const uint32_t kcap = (uint32_t)wsp.key_slots;   // 0: no key set
-    const strict_region_t rg = strict_region_plan(slice, kcap);
-    if (rg.bytes > strict_triage_bytes(wsp.triage_cap, wsp.key_slots_cap)) return hipErrorInvalidValue;
-    char* const region = static_cast<char*>(wsp.triage);
-    uint32_t* const xs = static_cast<uint32_t*>(wsp.triage);
-    uint32_t* const list = reinterpret_cast<uint32_t*>(region + rg.list);
-    uint32_t* const keyslot = kcap ? reinterpret_cast<uint32_t*>(region + rg.keyslot) : nullptr;
-    uint32_t* const count = reinterpret_cast<uint32_t*>(region + rg.block);
-    uint32_t* const nkeys = count + 1;
-    unsigned long long* const stats = reinterpret_cast<unsigned long long*>(region + rg.block + 8);
-    unsigned long long* const with_ctr =
-        reinterpret_cast<unsigned long long*>(region + rg.block + 1024);
-    uint32_t* const kslots = reinterpret_cast<uint32_t*>(region + rg.slots);
-    uint32_t* const kflags = reinterpret_cast<uint32_t*>(region + rg.kflags);
-    ge_cached_pk* const ktabs = reinterpret_cast<ge_cached_pk*>(region + rg.ktabs);
-    if (kcap) {
-      hipError_t e = hipMemsetAsync(stats, 0, kTriageBlockBytes - 8, stream);
-      if (e != hipSuccess) return e;
-    }
-    const keyspec ks8 = keyspec_for(8);
-    const uint32_t hot_cap = (uint32_t)wsp.comb_keys;
-    const comb_region_t cg = comb_region_plan(slice, kcap, hot_cap);
-    if (comb_on && (wsp.comb_min == 0 ||
-                    cg.bytes > strict_comb_bytes(wsp.triage_cap, wsp.key_slots_cap, wsp.comb_keys_cap)))
-      return hipErrorInvalidValue;
-    char* const cregion = comb_on ? static_cast<char*>(wsp.comb) : nullptr;
-    uint32_t* const nhot = reinterpret_cast<uint32_t*>(cregion);
-    uint32_t* const tcount = nhot + 1;
-    // with registered signers the skip test of the slice's comb kernels, the to-do list and the
-    // triage is "no hot key and no registered key": nlive; without them it is nhot, as before
-    const bool reg_on = comb_on && sg.n != 0;
-    uint32_t* const nlive = reg_on ? nhot + 2 : nhot;
-    unsigned long long* const cstats =
-        reinterpret_cast<unsigned long long*>(cregion + kCombStatsAt);
-    unsigned long long* const lanes = reinterpret_cast<unsigned long long*>(cregion + kCombLanesAt);
-    uint32_t* const todo = reinterpret_cast<uint32_t*>(cregion + cg.todo);
-    uint32_t* const uses = comb_on ? reinterpret_cast<uint32_t*>(cregion + cg.uses) : nullptr;
-    uint32_t* const hotidx = reinterpret_cast<uint32_t*>(cregion + cg.hotidx);
-    uint32_t* const match = reinterpret_cast<uint32_t*>(cregion + cg.match);
-    uint32_t* const hotrow = reinterpret_cast<uint32_t*>(cregion + cg.hotrow);
-    uint32_t* const hok = reinterpret_cast<uint32_t*>(cregion + cg.hok);
-    ge_niels_pad* const htabs = reinterpret_cast<ge_niels_pad*>(cregion + cg.tabs);
-    if (comb_on) {
-      hipError_t e = hipMemsetAsync(cstats, 0, kCombBlockBytes - kCombStatsAt, stream);
-      if (e != hipSuccess) return e;
-    }
-    {
-      int dev = 0;
-      if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
-        std::lock_guard<std::mutex> g(g_keyset_m);
-        g_keyset_last[dev] = keyset_record_t{region + rg.block, n, true, kcap != 0, cregion};
-      }
-    }
-    // equal slices of at most `slice` items
-    const uint64_t nsl = (n + slice - 1) / slice;
-    const uint64_t per = (n + nsl - 1) / nsl;
-    for (uint64_t i0 = 0; i0 < n; i0 += per) {
-      const uint64_t ns = std::min(per, n - i0);
-      hipError_t e = hipMemsetAsync(count, 0, 8, stream);   // count and nkeys
-      if (e != hipSuccess) return e;
-      if (kcap) {
-        // the slice's key set: each key's slot, then each slot's flags and table, once
-        e = hipMemsetAsync(kslots, 0, 4 * (size_t)kcap, stream);
-        if (e != hipSuccess) return e;
-        if (comb_on) {
-          e = hipMemsetAsync(nhot, 0, kCombSliceBytes, stream);   // nhot, the to-do count, nlive
-          if (e == hipSuccess) e = hipMemsetAsync(uses, 0, 4 * (size_t)kcap, stream);
-          if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(k_strict_keys_probe, dim3(grid_for(ns, 256)), dim3(256), 0, stream,
-                           pks, i0, ns, kslots, kcap, kcap / 2, nkeys, keyslot, with_ctr, uses);
-        hipLaunchKernelGGL(k_strict_keys_build, dim3(grid_for(kcap, 256)), dim3(256), 0, stream,
-                           pks, i0, kslots, kcap, kflags, ktabs, stats);
-      }
-      if (comb_on) {
-        // the slice's hot keys and their 8-bit comb tables, then the comb check of their items:
-        // a pass is status 0 (k_strict_keyed, or k_strict_keyed_inv for the x parity); every
-        // other item of the slice goes on the to-do list, with the comb's verdict in the entry
-        // when its sum ran (the triage then settles the item without the ladder). X' / Z' and the state use the
-        // region's planes 0-20, which the triage overwrites afterwards.
-        if (reg_on)
-          hipLaunchKernelGGL(k_strict_signers_match, dim3(grid_for(kcap, 256)), dim3(256), 0,
-                             stream, pks, i0, kslots, kcap, kflags,
-                             signers_view{sg.keys, sg.slots, sg.cap}, match, nlive, cstats + 3);
-        hipLaunchKernelGGL(k_strict_comb_select, dim3(grid_for(kcap, 256)), dim3(256), 0, stream,
-                           kslots, kcap, kflags, uses, wsp.comb_min, hot_cap, nhot, hotidx, hotrow,
-                           cstats, reg_on ? match : nullptr, reg_on ? sg.n : 0u,
-                           reg_on ? nlive : nullptr);
-        hipError_t e2 = launch_key_tables_rows(pks + 8 * i0, hotrow, nhot, hot_cap, ks8, htabs, hok,
-                                               stream);
-        if (e2 != hipSuccess) return e2;
-        const vote_planes_t vp{xs, xs + 20 * slice, slice, nullptr};
-        const key_tables_t hk{htabs, hok, keyslot, ks8};
-        if (reg_on)
-          hipLaunchKernelGGL(k_strict_keyed_signers, dim3(grid_for(ns, 256)), dim3(256), 0, stream,
-                             msgs, msg_stride_words, pks, sigs, i0, ns, status, hk, bcomb, vp,
-                             hotidx, nhot, nlive, sg.tabs, sg.ok, sg.n);
-        else
-          hipLaunchKernelGGL(k_strict_keyed<true>, dim3(grid_for(ns, 256)), dim3(256), 0, stream,
-                             msgs, msg_stride_words, pks, sigs, i0, ns, status, hk, bcomb, vp, 0,
-                             hotidx, nhot, cstats + 1);
-        const uint64_t nchunks = std::min<uint64_t>(ns, 256ull * 4 * 2 * 64);
-        hipLaunchKernelGGL(k_strict_keyed_inv, dim3(grid_for(nchunks, 256)), dim3(256), 0, stream,
-                           i0, ns, nchunks, status, vp, nlive);
-        if (reg_on)
-          hipLaunchKernelGGL(k_strict_signers_count, dim3(grid_for(ns, 256 * kTodoPer)), dim3(256),
-                             0, stream, ns, keyslot, hotidx, nhot, nlive, sg.n, vp.state, lanes);
-        hipLaunchKernelGGL(k_strict_todo_list, dim3(grid_for(ns, 256 * kTodoPer)), dim3(256), 0,
-                           stream, ns, vp.state, todo, tcount, nlive, comb_decide);
-      }
-      hipLaunchKernelGGL(k_strict_triage, dim3(grid_for(ns, 256)), dim3(256), 0, stream, msgs,
-                         msg_stride_words, pks, sigs, i0, ns, status, xs, slice, list, count,
-                         keyslot, kflags, comb_on ? todo : nullptr, tcount,
-                         comb_on ? cstats + 2 : nullptr, nlive,
-                         comb_on ? lanes + 3 * kCombStatLanes : nullptr);
-      hipLaunchKernelGGL(k_verify_strict_pre,
-                         dim3(std::min<uint64_t>(strict_grid(), grid_for(ns, 256))), dim3(256),
-                         0, stream, msgs, msg_stride_words, pks, sigs, i0, list, count, xs,
-                         slice, status, static_cast<ge_cached_pk*>(workspace), btw, ktabs,
-                         comb_on ? cstats + 4 : nullptr);
-    }
-    if (bitmap)
-      hipLaunchKernelGGL(k_status_bitmap, dim3(grid_for(n, 256)), dim3(256), 0, stream, status,
-                         n, bitmap);
-    return hipGetLastError();
+  // equal slices of at most p.slice items
+  const uint64_t nsl = (in.n + p.slice - 1) / p.slice;
+  const uint64_t per = (in.n + nsl - 1) / nsl;
+  for (uint64_t i0 = 0; i0 < in.n; i0 += per) {
+    e = strict_two_pass_slice(in, ws, tv, cv, btw, bcomb, i0, std::min(per, in.n - i0));
+    if (e != hipSuccess) return e;
   }
-  if (!kt.vote_key) {
-    hipLaunchKernelGGL(k_verify_strict<false>, dim3(grid), dim3(256), 0,
-                       stream, msgs,
-                       msg_stride_words, pks, sigs, n, status, bitmap,
-                       static_cast<ge_cached_pk*>(workspace), kt, btw, bcomb, nullptr, nullptr);
-    return hipGetLastError();
-  }
-  if (kf && kf[0] == '0') {
-    hipLaunchKernelGGL(k_verify_strict<true>, dim3(grid), dim3(256), 0, stream, msgs,
-                       msg_stride_words, pks, sigs, n, status, bitmap,
-                       static_cast<ge_cached_pk*>(workspace), kt, btw, bcomb, nullptr, nullptr);
-    return hipGetLastError();
-  }
-  // keyed fast path (k_strict_keyed above), slice by slice through the workspace
+  if (in.bitmap)
+    hipLaunchKernelGGL(k_status_bitmap, dim3(grid_for(in.n, 256)), dim3(256), 0, in.stream,
+                       in.status, in.n, in.bitmap);
+  return hipGetLastError();
+}
+
+// One pass of k_verify_strict over every item: the unkeyed launch with NW_STRICT_TRIAGE=0
+// (bcomb null) and the committee-keyed one with NW_STRICT_KEYED_FAST=0.
+hipError_t launch_strict_one_pass(const strict_items_t& in, void* workspace,
+                                  const key_tables_t& kt, const ge_niels_pad* btw,
+                                  const ge_niels_pad* bcomb) {
+  const dim3 grid(std::min<uint64_t>(strict_grid(), grid_for(in.n, 256)));
+  hipLaunchKernelGGL(kt.vote_key ? k_verify_strict<true> : k_verify_strict<false>, grid, dim3(256),
+                     0, in.stream, in.msgs, in.msg_stride_words, in.pks, in.sigs, in.n, in.status,
+                     in.bitmap, static_cast<ge_cached_pk*>(workspace), kt, btw, bcomb, nullptr,
+                     nullptr);
+  return hipGetLastError();
+}
+
+// The committee-keyed fast path (k_strict_keyed above), slice by slice through the workspace:
+// the per-lane table region holds the slice's limb planes, the tail its list and count.
+hipError_t launch_strict_keyed_fast(const strict_items_t& in, void* workspace,
+                                    const key_tables_t& kt, const ge_niels_pad* btw,
+                                    const ge_niels_pad* bcomb) {
+  hipStream_t const stream = in.stream;
   const uint64_t S = std::min<uint64_t>(kKeyedSliceMax, strict_tabs_bytes() / (4 * 21)) & ~63ull;
   uint32_t* base = static_cast<uint32_t*>(workspace);
   uint32_t* list = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + strict_tabs_bytes());
   uint32_t* count = list + kKeyedSliceMax;
   const vote_planes_t vp{base, base + 20 * S, S, nullptr};
-  for (uint64_t i0 = 0; i0 < n; i0 += S) {
-    const uint64_t ns = std::min(S, n - i0);
+  for (uint64_t i0 = 0; i0 < in.n; i0 += S) {
+    const uint64_t ns = std::min(S, in.n - i0);
+    const dim3 lanes(256), per_item(grid_for(ns, 256));
     hipError_t e = hipMemsetAsync(count, 0, 4, stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_strict_keyed<false>, dim3(grid_for(ns, 256)), dim3(256), 0, stream, msgs,
-                       msg_stride_words, pks, sigs, i0, ns, status, kt, bcomb, vp, i0, nullptr,
-                       nullptr, nullptr);
-    const uint64_t nchunks = std::min<uint64_t>(ns, 256ull * 4 * 2 * 64);
-    hipLaunchKernelGGL(k_strict_keyed_inv, dim3(grid_for(nchunks, 256)), dim3(256), 0, stream,
-                       i0, ns, nchunks, status, vp, nullptr);
-    hipLaunchKernelGGL(k_strict_keyed_list, dim3(grid_for(ns, 256)), dim3(256), 0, stream, i0,
-                       ns, vp.state, list, count);
+    hipLaunchKernelGGL(k_strict_keyed<false>, per_item, lanes, 0, stream, in.msgs,
+                       in.msg_stride_words, in.pks, in.sigs, i0, ns, in.status, kt, bcomb, vp, i0,
+                       nullptr, nullptr, nullptr);
+    const uint64_t nchunks = inv_chunks(ns);
+    hipLaunchKernelGGL(k_strict_keyed_inv, dim3(grid_for(nchunks, 256)), lanes, 0, stream, i0, ns,
+                       nchunks, in.status, vp, nullptr);
+    hipLaunchKernelGGL(k_strict_keyed_list, per_item, lanes, 0, stream, i0, ns, vp.state, list,
+                       count);
     // the leftovers: full verification (exact status codes), the tables over the planes
-    hipLaunchKernelGGL(k_verify_strict<true>, dim3(std::min<uint64_t>(strict_grid(), grid_for(ns, 256))),
-                       dim3(256), 0, stream, msgs, msg_stride_words, pks, sigs, ns, status,
-                       bitmap, static_cast<ge_cached_pk*>(workspace), kt, btw, bcomb, list, count);
+    hipLaunchKernelGGL(k_verify_strict<true>, dim3(std::min<uint64_t>(strict_grid(), per_item.x)),
+                       lanes, 0, stream, in.msgs, in.msg_stride_words, in.pks, in.sigs, ns,
+                       in.status, in.bitmap, static_cast<ge_cached_pk*>(workspace), kt, btw, bcomb,
+                       list, count);
   }
-  if (bitmap)
-    hipLaunchKernelGGL(k_status_bitmap, dim3(grid_for(n, 256)), dim3(256), 0, stream, status, n,
-                       bitmap);
+  if (in.bitmap)
+    hipLaunchKernelGGL(k_status_bitmap, dim3(grid_for(in.n, 256)), dim3(256), 0, stream, in.status,
+                       in.n, in.bitmap);
   return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_verify_strict(const uint32_t* msgs, uint32_t msg_stride_words,
+                                const uint32_t* pks, const uint32_t* sigs, uint64_t n,
+                                int32_t* status, uint64_t* bitmap, const strict_ws_t& ws,
+                                hipStream_t stream, const key_tables_t* keys) {
+  if (n == 0) return hipSuccess;
+  const strict_items_t in{msgs, msg_stride_words, pks, sigs, n, status, bitmap, stream};
+  const key_tables_t kt = keys ? *keys : key_tables_t{nullptr, nullptr, nullptr, {}};
+  const ge_niels_pad* btw = nullptr;
+  const ge_niels_pad* bcomb = nullptr;
+  hipError_t e = btab_for_current_device(0, &btw);
+  if (e == hipSuccess && kt.vote_key) e = btab_for_current_device(1, &bcomb);
+  if (e != hipSuccess) return e;
+  if (!kt.vote_key)
+    return strict_triage_on() ? launch_strict_two_pass(in, ws, btw)
+                              : launch_strict_one_pass(in, ws.base, kt, btw, nullptr);
+  return env_is_zero("NW_STRICT_KEYED_FAST") ? launch_strict_one_pass(in, ws.base, kt, btw, bcomb)
+                                             : launch_strict_keyed_fast(in, ws.base, kt, btw, bcomb);
 }
 
 size_t votes_keyed_bytes_per_vote() { return 4 * 22; }   // 20 limb planes, state, perm
@@ -1945,7 +1926,7 @@ hipError_t launch_votes_keyed(const uint32_t* cert_digest, const uint64_t* cvo, 
                        cert_digest, vote_cert, v0, nv, pks, sigs, pre1, pre2, hdr_st, keys, bcomb,
                        cert_ok, vp);
     // chunks: ~2 waves per SIMD of lanes, each over nv / nchunks votes (>= 1)
-    const uint64_t nchunks = std::min<uint64_t>(nv, 256ull * 4 * 2 * 64);
+    const uint64_t nchunks = inv_chunks(nv);
     hipLaunchKernelGGL(k_votes_keyed_inv, dim3(grid_for(nchunks, 256)), dim3(256), 0, stream,
                        vote_cert, v0, nv, nchunks, cert_ok, vp);
   }
@@ -1982,7 +1963,7 @@ hipError_t launch_batch_signers(const uint32_t* digests, const uint64_t* offsets
     // inversion per pending vote: the lanes are idle otherwise, and chunks of 8 votes measured
     // slower where latency counts (a lone 10,000-vote call 0.311 against 0.294-0.306 ms, a 34-vote
     // call 0.257 against 0.240-0.242) and equal on 262,144 votes and above (profiles/r12a)
-    const uint64_t nchunks = std::min<uint64_t>(nitems, 256ull * 4 * 2 * 64);
+    const uint64_t nchunks = inv_chunks(nitems);
     hipLaunchKernelGGL(k_batch_signers_inv, dim3(grid_for(nchunks, 256)), dim3(256), 0, stream,
                        offsets, nbatches, nitems, nchunks, batch_ok, vp);
   }

@@ -102,8 +102,9 @@ class Lease {
   ~Lease() { (void)release(); }
   int acquire(int dev_index, hipStream_t stream);
   // The device's strict workspace (nw::strict_workspace_bytes(), allocated once) and, for an
-  // unkeyed launch of n items (n = 0: keyed, none), the two-pass path's slice
-  // (nw::strict_triage_bytes(nw::strict_triage_slice(n)), grow-only).
+  // unkeyed launch of n items (n = 0: keyed, none), that launch's plan (nw::strict_launch_plan)
+  // and the regions it needs: the two-pass path's slice (nw::strict_triage_bytes(plan.slice,
+  // plan.key_slots)) and, with the comb path, its tables (nw::strict_comb_bytes); grow-only.
   int strict_ws(nw::strict_ws_t* out, size_t n);
   // Key tables for nkeys keys (grow-only at one comb width, nw_api.cpp key_width): tabs
   // (nw::key_tables_bytes) and ok words, their layout (ks), plus the reuse state of

@@ -315,7 +315,7 @@ NW_HD void keyset_build(const uint32_t* slots, uint32_t s, const uint32_t* pks, 
   if (ok) build_table8(ktabs + 8 * (uint64_t)s, P, K.k.d2);
 }
 
-// A key of the set is hot for the comb check (nw_kernels.h strict_comb_plan) when enough items of
+// A key of the set is hot for the comb check (nw_kernels.h strict_launch_plan) when enough items of
 // the slice use it to pay for its 8-bit comb tables and it can pass at all: a key that does
 // not decode or has small order never does.
 // A key's uses are estimated from a fixed sample of the slice's items, one in kCombSample,

@@ -167,6 +167,68 @@ def test_slice_without_registered_or_hot_key(corpus):
     assert stats == [0, 0, 0, 300]
 
 
+_READERS = {"keyset": 3, "comb": 4, "decided": 2, "signers": 3}
+
+
+def _readers(order):
+    """The counters of the last launch through the four readers, called in `order`."""
+    L = _lib.lib()
+    stream = ctypes.c_void_p(torch.cuda.current_stream(torch.device("cuda", 0)).cuda_stream)
+    out = {}
+    for name in order:
+        buf = (ctypes.c_uint64 * _READERS[name])()
+        assert getattr(L, f"nw_dev_strict_{name}_stats")(buf, stream) == 0, L.nw_last_error()
+        out[name] = [int(x) for x in buf]
+    return out
+
+
+def test_counter_readers_agree(corpus, monkeypatch):
+    """200 items in four slices (NW_TRIAGE_SLICE=64) at NW_STRICT_COMB_MIN=16: two keys of 80 and
+    60 uses, one registered key of 40, 20 strangers of one use each, nine broken signatures. The
+    four readers project one snapshot of the launch's counters: whatever the order and however
+    often they are called they give the same values, which satisfy the identities between them;
+    without the comb path, and without the key set, they give the fallback tuples."""
+    monkeypatch.setenv("NW_TRIAGE_SLICE", "64")
+    monkeypatch.setenv("NW_STRICT_COMB_MIN", "16")
+    rng = np.random.Generator(np.random.PCG64(1013))
+    kps = [corpus["kps"][0], corpus["kps"][8], corpus["kps"][9]]
+    kps += [O.keypair_from_seed(rng.bytes(32)) for _ in range(20)]
+    n = 200
+    key_of = [[1, 1, 1, 1, 2, 2, 2, 0, 0, 3 + i // 10][i % 10] for i in range(n)]
+    m, p, s = _sign_rows(rng, kps, key_of)
+    for i in range(0, n, 23):
+        s[i, rng.integers(0, 64)] ^= np.uint8(1 << rng.integers(0, 8))
+    exp = O.verify_strict_many(m, p, s).astype(np.int32)
+    assert 0 < int((exp != 0).sum()) <= 9
+    _set(corpus["keys"][:1])
+    st, bits, stats, ss = _launch(m, p, s)
+    assert np.array_equal(st, exp) and np.array_equal(bits, exp == 0)
+    fwd, rev = list(_READERS), list(_READERS)[::-1]
+    got = [_readers(fwd), _readers(fwd), _readers(rev), _readers(rev)]
+    print("readers:", got[0])
+    assert all(g == got[0] for g in got[1:]), got
+    keyset, comb, decided, signers = (got[0][k] for k in fwd)
+    assert comb == stats and signers == ss
+    assert comb[2] + comb[3] == n
+    assert keyset[1] + keyset[2] == n
+    assert decided[0] + decided[1] <= comb[3]
+    assert signers[2] <= signers[1] <= comb[1]
+    monkeypatch.setenv("NW_STRICT_COMB", "0")
+    st, bits, _, _ = _launch(m, p, s)
+    assert np.array_equal(st, exp) and np.array_equal(bits, exp == 0)
+    for got in (_readers(fwd), _readers(rev)):
+        assert got["comb"] == [0, 0, 0, n] and got["decided"] == [0, 0]
+        assert got["signers"] == [0, 0, 0]
+        assert got["keyset"] == keyset          # the key set does not depend on the comb path
+    monkeypatch.delenv("NW_STRICT_COMB")
+    monkeypatch.setenv("NW_STRICT_KEYS", "0")
+    st, bits, _, _ = _launch(m, p, s)
+    assert np.array_equal(st, exp) and np.array_equal(bits, exp == 0)
+    for got in (_readers(fwd), _readers(rev)):
+        assert got["keyset"] == [0, 0, n] and got["comb"] == [0, 0, 0, n]
+        assert got["decided"] == [0, 0] and got["signers"] == [0, 0, 0]
+
+
 def test_replacing_the_registry(corpus):
     """Set A, a disjoint set B, then none: the keys matched follow the registry each time, and
     the cleared registry is the launch sequence of before."""

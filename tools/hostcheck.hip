@@ -855,6 +855,36 @@ int hc_ge_ops(int op, uint32_t n, const uint32_t* A, const uint32_t* B, const in
   return 0;
 }
 
+// The two regions of a two-pass strict launch (nw_strict_layout.hpp), for
+// tests/test_strict_layout_cpu.py: every offset and the bytes of strict_region_plan (7 values),
+// then of comb_region_plan with the 8-bit tables of hot_cap keys (8; the tables' bytes as
+// nw_batch.hip key_tables_bytes gives them), then the offsetof of every field of triage_block_t
+// and its size (5) and of comb_block_t and its size (13). Returns the number of values written.
+int hc_strict_layout(uint64_t slice, uint64_t key_slots, uint64_t hot_cap, uint64_t out[]) {
+  const strict_region_t r = strict_region_plan(slice, key_slots);
+  const keyspec ks8 = keyspec_for(8);
+  const uint64_t nk = hot_cap ? hot_cap : 1;
+  const comb_region_t c = comb_region_plan(
+      slice, key_slots, hot_cap,
+      sizeof(ge_niels_pad) * (uint64_t)ks8.tab * nk + sizeof(ge) * (2 + keyspec_tables(ks8)) * nk);
+  const uint64_t v[] = {
+      r.list, r.keyslot, r.block, r.slots, r.kflags, r.ktabs, r.bytes,
+      c.todo, c.uses, c.hotidx, c.match, c.hotrow, c.hok, c.tabs, c.bytes,
+      offsetof(triage_block_t, count), offsetof(triage_block_t, nkeys),
+      offsetof(triage_block_t, keys_tabulated), offsetof(triage_block_t, with_slot),
+      sizeof(triage_block_t),
+      offsetof(comb_block_t, nhot), offsetof(comb_block_t, todo_count),
+      offsetof(comb_block_t, nlive), offsetof(comb_block_t, hot_keys),
+      offsetof(comb_block_t, checked), offsetof(comb_block_t, listed),
+      offsetof(comb_block_t, matched), offsetof(comb_block_t, laddered),
+      offsetof(comb_block_t, lane_checked), offsetof(comb_block_t, lane_reg_items),
+      offsetof(comb_block_t, lane_reg_passed), offsetof(comb_block_t, lane_settled),
+      sizeof(comb_block_t)};
+  const int count = (int)(sizeof(v) / sizeof(v[0]));
+  for (int i = 0; i < count; ++i) out[i] = v[i];
+  return count;
+}
+
 }
 
 #ifdef KEYSET_SAN_MAIN
