@@ -252,7 +252,13 @@ int nw_dev_strict_decided_stats(uint64_t out[2], void* stream);
  * set every vote of such a call first takes the comb check under its registered key; a batch all
  * of whose votes pass is Ok for every coefficient set and is settled there, every other batch
  * (a vote that fails, a signer that is not registered, a registered key with a torsion component)
- * runs the ordinary verify_batch, which names its status and failing index. No verdict depends on
+ * runs the ordinary verify_batch, which names its status and failing index. That run covers only
+ * the votes of the batch that did not pass: a passed vote's terms cancel in the batch equation
+ * for every coefficient set and none of the checks before the equation can fail on it, so it is
+ * neither decompressed, hashed, tabulated nor added, and the others keep their positions. A set
+ * that holds most of a caller's signers, not all, therefore still saves most of the work of a
+ * batch that carries one unknown signer or one broken vote. NW_BATCH_SIGNERS_VOTES=0 (read per
+ * call) runs every vote of a batch that is sent on, as before. No verdict depends on
  * the set. NW_BATCH_SIGNERS=0 turns this off, NW_BATCH_SIGNERS_MIN_VOTES (default 1) is the
  * smallest call that takes it (both read per call; NW_STRICT_COMB does not govern it). It needs
  * the device's B comb table: where that cannot be allocated the calls run as without a set.
@@ -273,6 +279,11 @@ int nw_dev_strict_signers_stats(uint64_t out[3], void* stream);
  * included), out[3] = batches sent on to the ordinary verify_batch. Calls that did not take the
  * path count nothing. NW_E_NO_DEVICE without a device. */
 int nw_batch_signers_stats(uint64_t out[4]);
+/* The votes of the batches those calls sent on (out[3] above), summed and delivered by the same
+ * rules: out[0] = votes left out of their batch's sum because the comb check passed them,
+ * out[1] = votes that ran in it. Under NW_BATCH_SIGNERS_VOTES=0 out[0] does not move and out[1]
+ * counts every vote of such a batch. NW_E_NO_DEVICE without a device. */
+int nw_batch_signers_vote_stats(uint64_t out[2]);
 
 /* ---- aggregation service: one request per message, coalesced into device jobs ------- */
 /* The front end a crypto-gpu crate puts behind the primary's per-message checks: Core

@@ -71,6 +71,7 @@ def lib() -> ctypes.CDLL:
         "nw_strict_signers_count": ([P], I),
         "nw_dev_strict_signers_stats": ([P, P], I),
         "nw_batch_signers_stats": ([P], I),
+        "nw_batch_signers_vote_stats": ([P], I),
         "nw_keypair_from_seed_many": ([P, S, P], I),
         "nw_sign_many": ([P, S, P, S, S, P], I),
         "nw_dev_keypair_from_seed_many": ([P, S, P, P], I),

@@ -32,7 +32,8 @@ __all__ = ["Digest", "Hash", "PublicKey", "SecretKey", "Signature", "CryptoError
            "EngineError", "generate_keypair", "keypair_from_seed_many", "sign_many",
            "sha512_digest", "sha512_digest32_many", "verify_strict_many",
            "verify_batch_many", "set_strict_signers", "strict_signers_count",
-           "strict_signers_stats", "batch_signers_stats"]
+           "strict_signers_stats", "batch_signers_stats",
+           "batch_signers_vote_stats"]
 
 
 class CryptoError(Exception):
@@ -284,6 +285,14 @@ def batch_signers_stats() -> tuple[int, int, int, int]:
     out = (ctypes.c_uint64 * 4)()
     check(_lib.lib().nw_batch_signers_stats(out), "nw_batch_signers_stats")
     return int(out[0]), int(out[1]), int(out[2]), int(out[3])
+
+
+def batch_signers_vote_stats() -> tuple[int, int]:
+    """(votes left out of their batch's sum, votes that ran in it) over the batches those calls
+    sent on (nw_batch_signers_vote_stats), summed and delivered like batch_signers_stats."""
+    out = (ctypes.c_uint64 * 2)()
+    check(_lib.lib().nw_batch_signers_vote_stats(out), "nw_batch_signers_vote_stats")
+    return int(out[0]), int(out[1])
 
 
 def verify_batch_many(digests: np.ndarray, pks: np.ndarray, sigs: np.ndarray,

@@ -431,6 +431,66 @@ __global__ __launch_bounds__(256) void k_bv_items_chunked(
   bv_item_build(gi, gi - i0, b0 + ch.batch, digests, pks, sigs, z16, zkey, items, tabs, keys);
 }
 
+// The items of the listed votes only (launch_batch_signers' list of the votes that did not pass
+// the comb check, batch_votes_t: any order, the whole call's): a vote the check passed gets no
+// item, k_bv_chunks<true> leaves it out by its state. list[l], l < *count; the host sizes the
+// grid for every vote of the call, and a block at or past the count returns at its top. An
+// entry of another slice, or of a Pippenger batch (k_pip_points), is passed over.
+__global__ __launch_bounds__(256) void k_bv_items_listed(
+    const uint32_t* __restrict__ list, const uint32_t* __restrict__ count,
+    const uint32_t* __restrict__ digests, const uint64_t* __restrict__ offsets, uint64_t b0,
+    uint64_t b1, uint64_t i0, uint64_t i1, uint32_t pmin, const uint32_t* __restrict__ pks,
+    const uint32_t* __restrict__ sigs, const uint32_t* __restrict__ z16, z_key_t zkey,
+    bv_item* __restrict__ items, ge_cached* __restrict__ tabs) {
+  const uint32_t nl = *count;
+  if (blockIdx.x * blockDim.x >= nl) return;
+  const uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= nl) return;
+  const uint64_t gi = list[l];
+  if (gi < i0 || gi >= i1) return;
+  uint64_t lo = b0, hi = b1;
+  while (hi - lo > 1) {
+    const uint64_t mid = (lo + hi) >> 1;
+    if (offsets[mid] <= gi) lo = mid; else hi = mid;
+  }
+  if (offsets[lo + 1] - offsets[lo] >= pmin) return;   // k_pip_points
+  bv_item_build(gi, gi - i0, lo, digests, pks, sigs, z16, zkey, items, tabs,
+                key_tables_t{nullptr, nullptr, nullptr, {}});
+}
+
+// One lane per chunk of the plan: a chunk that holds a listed vote (state != kVotePass) goes
+// on the dense list k_bv_chunks<true> runs over (one atomic per wave; the order does not
+// matter, a chunk's output is indexed by its number in the plan); a chunk with none is a
+// chunk of a batch with several (a batch wholly passed is settled and has no chunks) and
+// writes what k_bv_combine expects of it: the identity, no failure. *nlive = 0 before.
+__global__ __launch_bounds__(256) void k_bv_live_chunks(
+    const bv_chunk* __restrict__ chunks, uint32_t nchunks, const uint32_t* __restrict__ ctotal,
+    const uint32_t* __restrict__ vstate, bv_chunk_out* __restrict__ out,
+    uint32_t* __restrict__ live, uint32_t* __restrict__ nlive) {
+  const uint32_t nch = min(nchunks, *ctotal);   // host bound, device total
+  if (blockIdx.x * blockDim.x >= nch) return;
+  const uint32_t ci = blockIdx.x * blockDim.x + threadIdx.x;
+  bool any = false;
+  if (ci < nch) {
+    const bv_chunk ch = chunks[ci];
+    for (uint32_t t = 0; t < ch.count && !any; ++t) any = vstate[ch.start + t] != kVotePass;
+    if (!any) {
+      bv_chunk_out o;
+      ge_identity(o.P);
+      o.first[0] = o.first[1] = o.first[2] = kNone;
+      o.pad = 0;
+      out[ci] = o;
+    }
+  }
+  const uint64_t m = __ballot(any);
+  if (m == 0) return;
+  const uint32_t lane = threadIdx.x & 63u, leader = (uint32_t)__builtin_ctzll(m);
+  uint32_t base = 0;
+  if (lane == leader) base = atomicAdd(nlive, (uint32_t)__builtin_popcountll(m));
+  base = (uint32_t)__shfl((int)base, (int)leader);
+  if (any) live[base + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull))] = ci;
+}
+
 // ------------------------------------------------------------------------------ chunks
 __device__ __forceinline__ int digit4(uint32_t word, int j) {
   return (int)((word >> ((j & 7) * 4)) & 15u) - 8;
@@ -491,12 +551,18 @@ __device__ __forceinline__ void add_key_entry(ge& acc, const ge_niels_pad* tab12
 //     before, -sum b = b_lo + 2^128 b_hi by 8-bit digits over j*B and j*2^128 B.
 // A lane whose chunk is keyed simply has no digits above window 32 when the wave runs the
 // long ladder for another lane (the identity doubles to itself).
+// kVotes (plain batches after the comb phase, batch_votes_t): the lanes run over the dense list
+// `live` of the chunks that hold a listed vote (*ctotal of them, k_bv_live_chunks), a chunk's
+// output keeps its number in the plan, and a vote whose vstate is kVotePass has no item and
+// adds nothing: its terms cancel for every coefficient.
+template <bool kVotes>
 __global__ __launch_bounds__(256) void k_bv_chunks(
     const bv_chunk* __restrict__ chunks, uint32_t nchunks, const uint64_t* __restrict__ offsets,
     uint64_t b0, uint64_t i0, const bv_item* __restrict__ items,
     const ge_cached* __restrict__ tabs, const ge_niels_pad* __restrict__ ktabs, keyspec ks,
     bv_chunk_out* __restrict__ out, int32_t* __restrict__ status,
-    uint64_t* __restrict__ fail_index, const uint32_t* __restrict__ ctotal) {
+    uint64_t* __restrict__ fail_index, const uint32_t* __restrict__ ctotal,
+    const uint32_t* __restrict__ vstate, const uint32_t* __restrict__ live_list) {
   __shared__ ge_niels s_btab[129];
   __shared__ ge_niels s_b128[129];
   const uint32_t ci = blockIdx.x * blockDim.x + threadIdx.x;
@@ -516,7 +582,9 @@ __global__ __launch_bounds__(256) void k_bv_chunks(
   }
   __syncthreads();
   const bool live = ci < nch;
-  const bv_chunk ch = chunks[live ? ci : nch - 1];
+  uint32_t cidx = live ? ci : nch - 1;   // the chunk's number in the plan
+  if constexpr (kVotes) cidx = live_list[cidx];
+  const bv_chunk ch = chunks[cidx];
   const uint64_t bidx = b0 + ch.batch;
   const uint64_t bstart = offsets[bidx];
   const uint64_t bn = offsets[bidx + 1] - bstart;
@@ -528,7 +596,14 @@ __global__ __launch_bounds__(256) void k_bv_chunks(
   sc bsum;
 #pragma unroll
   for (int j = 0; j < 8; ++j) bsum.w[j] = 0;
+  uint64_t out0 = 0, out1 = 0;   // kVotes: the chunk's votes left out (count <= kMaxChunk)
   for (uint32_t t = 0; t < ch.count; ++t) {
+    if constexpr (kVotes) {
+      if (vstate[ch.start + t] == kVotePass) {
+        if (t < 64) out0 |= 1ull << t; else out1 |= 1ull << (t - 64);
+        continue;
+      }
+    }
     const bv_item* it = items + l0 + t;
     const uint32_t f = it->flags;
     const uint32_t rel = (uint32_t)(ch.start + t - bstart);
@@ -561,6 +636,9 @@ __global__ __launch_bounds__(256) void k_bv_chunks(
     if (!live) continue;
 #pragma unroll 1
     for (uint32_t t = 0; t < ch.count; ++t) {
+      if constexpr (kVotes) {
+        if (((t < 64 ? out0 : out1) >> (t & 63u)) & 1ull) continue;
+      }
       const bv_item* it = items + l0 + t;
       const ge_cached* tab = tabs + 16 * (l0 + t);
       if (keyed) {
@@ -598,7 +676,7 @@ __global__ __launch_bounds__(256) void k_bv_chunks(
     o.first[1] = first[1];
     o.first[2] = first[2];
     o.pad = flags0;
-    out[ci] = o;
+    out[cidx] = o;
   }
 }
 
@@ -735,6 +813,7 @@ constexpr size_t pip_region_bytes(uint64_t n) {
          sizeof(ge) * kPipBins + sizeof(ge_cached) * kPipWin + 16 + 32 + sizeof(ge_cached);
 }
 // per-vote bytes grow slower than the item slots (2560 B), so the floor is the binding n
+static_assert(kMaxChunk <= 128, "k_bv_chunks<true> keeps a chunk's left-out votes in 128 bits");
 static_assert(pip_region_bytes(kPipFloor) <= 16 * sizeof(ge_cached) * kPipFloor,
               "Pippenger region does not fit its items' table slots");
 // certificate groups: >= kPipMin votes plus up to 256 committee keys
@@ -815,12 +894,37 @@ __device__ __forceinline__ void ge_shfl(ge& r, const ge& p, int src) {
 // batches only: in group mode A is a committee key) = decompress A. Three short chains
 // instead of one lane doing the scalars and A's decompression in series (the one-call
 // latency of config 1 is this kernel's longest lane).
+// A vote that contributes nothing to its Pippenger batch: zero digits (no bucket entry, its
+// points are never read), b = 0, no flags. Role 2 (plain batches) has nothing to write: role 0
+// clears the A lane's word.
+__device__ __forceinline__ void pip_point_neutral(int which, bv_item* it, const pip_region& reg,
+                                                  uint64_t nreg, uint64_t t) {
+  if (which == 1) {
+    it->pad = 0;
+  } else if (which == 0) {
+    it->z[0] = 0;
+#pragma unroll
+    for (int w = 0; w < kPipWin; ++w) reg.cd[w * nreg + t] = 0x80;
+#pragma unroll
+    for (int w = 0; w < kPipZWin; ++w) reg.zd[w * nreg + t] = 0x80;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) it->b[j] = 0;
+    it->flags = 0;
+    it->key = kNone;
+  }
+}
+
+// kVotes (plain batches after the comb phase): a vote whose vstate is kVotePass is neutral, as
+// a vote of a certificate decided before the votes is in group mode; neither of its points is
+// decompressed.
+template <bool kVotes>
 __device__ __forceinline__ void pip_point_do(
     int which, uint64_t li, const uint32_t* __restrict__ digests,
     const uint64_t* __restrict__ offsets, uint64_t b0, uint64_t b1, uint64_t i0, uint64_t i1,
     uint32_t pmin, const uint32_t* __restrict__ pks, const uint32_t* __restrict__ sigs,
     const uint32_t* __restrict__ z16, const z_key_t& zkey, bv_item* __restrict__ items,
-    ge_cached* __restrict__ tabs, const pip_group_t& grp, const batch_skip_t& sk) {
+    ge_cached* __restrict__ tabs, const pip_group_t& grp, const batch_skip_t& sk,
+    const uint32_t* __restrict__ vstate) {
   const uint64_t gi = i0 + li;
   if (gi >= i1) return;
   const uint64_t lo = batch_of(offsets, b0, b1, gi);
@@ -832,6 +936,12 @@ __device__ __forceinline__ void pip_point_do(
   const pip_region reg = pip_at(tabs, bs - i0, nreg);
   const curve_consts& K = g_bc.k;
   bv_item* it = items + li;
+  if constexpr (kVotes) {
+    if (vstate[gi] == kVotePass) {
+      pip_point_neutral(which, it, reg, nreg, t);
+      return;
+    }
+  }
   uint64_t dig = lo;   // digest index: the batch, or in group mode the vote's certificate
   if (group) {
     const uint64_t c0 = lo * grp.certs_per_group;
@@ -839,19 +949,7 @@ __device__ __forceinline__ void pip_point_do(
     dig = batch_of(grp.cert_vote_offsets, c0, c1, gi);
     if (grp.pre1[dig] != 0 || grp.hdr_st[dig] != 0 || grp.pre2[dig] != 0) {
       // decided before the votes: contributes nothing
-      if (which == 1) {
-        it->pad = 0;
-      } else if (which == 0) {
-        it->z[0] = 0;
-#pragma unroll
-        for (int w = 0; w < kPipWin; ++w) reg.cd[w * nreg + t] = 0x80;
-#pragma unroll
-        for (int w = 0; w < kPipZWin; ++w) reg.zd[w * nreg + t] = 0x80;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) it->b[j] = 0;
-        it->flags = 0;
-        it->key = kNone;
-      }
+      pip_point_neutral(which, it, reg, nreg, t);
       return;
     }
   }
@@ -936,15 +1034,17 @@ __device__ __forceinline__ void pip_point_do(
   it->key = key;
 }
 
+template <bool kVotes>
 __global__ __launch_bounds__(256, 3) void k_pip_points(
     const uint32_t* __restrict__ digests, const uint64_t* __restrict__ offsets, uint64_t b0,
     uint64_t b1, uint64_t i0, uint64_t i1, uint32_t pmin, const uint32_t* __restrict__ pks,
     const uint32_t* __restrict__ sigs, const uint32_t* __restrict__ z16, z_key_t zkey,
     bv_item* __restrict__ items, ge_cached* __restrict__ tabs, pip_group_t grp,
-    uint32_t roles, uint32_t role0, batch_skip_t sk) {
+    uint32_t roles, uint32_t role0, batch_skip_t sk, const uint32_t* __restrict__ vstate) {
   const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, wave = g >> 6;
-  pip_point_do((int)(role0 + wave % roles), (wave / roles) * 64 + (g & 63), digests, offsets, b0,
-               b1, i0, i1, pmin, pks, sigs, z16, zkey, items, tabs, grp, sk);
+  pip_point_do<kVotes>((int)(role0 + wave % roles), (wave / roles) * 64 + (g & 63), digests,
+                       offsets, b0, b1, i0, i1, pmin, pks, sigs, z16, zkey, items, tabs, grp, sk,
+                       vstate);
 }
 
 // Group mode: per group, sum_i c_i per committee key (LDS, 64-bit limb sums), reduced mod l,
@@ -2320,8 +2420,9 @@ __global__ __launch_bounds__(256) void k_pip_points_sorted(
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
     }
     if (grp64 < wv)
-      pip_point_do(which, grp64 * 64 + (uint64_t)(tid & 63), digests, offsets, bidx, bidx + 1,
-                   i0, i1, 0, pks, sigs, z16, zkey, items, tabs, nogrp, batch_skip_t{nullptr, 1});
+      pip_point_do<false>(which, grp64 * 64 + (uint64_t)(tid & 63), digests, offsets, bidx,
+                          bidx + 1, i0, i1, 0, pks, sigs, z16, zkey, items, tabs, nogrp,
+                          batch_skip_t{nullptr, 1}, nullptr);
     if (t < nb0) {
       // the workgroup's digits, then ONE count (a release per wave is an L2 write-back
       // each: 628 of them slowed the decompressions 73 -> 114 us); the decompressions signal
@@ -2363,7 +2464,7 @@ hipError_t launch_pip(const uint32_t* digests, const uint64_t* offsets, uint64_t
                 const pip_group_t& grp, hipStream_t stream,
                 uint32_t* fctr, const input_gate_t* gate = nullptr, uint32_t* done = nullptr,
                 uint32_t done_seq = 0, const batch_skip_t& sk = batch_skip_t{nullptr, 1},
-                const uint32_t* pip_count = nullptr) {
+                const uint32_t* pip_count = nullptr, const uint32_t* vstate = nullptr) {
   const bool group = grp.cert_vote_offsets != nullptr;
   const uint32_t extra = group ? grp.nkeys : 0;   // key sums
   const uint32_t roles = group ? 2 : 3;
@@ -2384,9 +2485,15 @@ hipError_t launch_pip(const uint32_t* digests, const uint64_t* offsets, uint64_t
                        (uint32_t)wv, ks, fctr, head_stamps(npb + kPipWin * ks),
                        gate ? *gate : input_gate_t{nullptr, 0u, 64u});
   } else {
-    hipLaunchKernelGGL(k_pip_points, dim3((unsigned)((wv * roles * 64 + 255) / 256)), dim3(256),
-                       0, stream, digests, offsets, b, e, i0, i1, pmin, pks, sigs, z16, zkey,
-                       w.items, w.tabs, grp, roles, 0u, sk);
+    const dim3 gp((unsigned)((wv * roles * 64 + 255) / 256));
+    if (vstate)
+      hipLaunchKernelGGL(k_pip_points<true>, gp, dim3(256), 0, stream, digests, offsets, b, e, i0,
+                         i1, pmin, pks, sigs, z16, zkey, w.items, w.tabs, grp, roles, 0u, sk,
+                         vstate);
+    else
+      hipLaunchKernelGGL(k_pip_points<false>, gp, dim3(256), 0, stream, digests, offsets, b, e, i0,
+                         i1, pmin, pks, sigs, z16, zkey, w.items, w.tabs, grp, roles, 0u, sk,
+                         nullptr);
     if (group)
       hipLaunchKernelGGL(k_grp_keys, dim3((unsigned)npip), dim3(1024), 0, stream, offsets, b,
                          i0, pmin, w.items, w.tabs, grp);
@@ -2473,9 +2580,15 @@ hipError_t launch_verify_batch(const uint32_t* digests, const uint64_t* offsets,
                                const key_tables_t* keys, const uint32_t* skip_group_ok,
                                uint64_t skip_per_group, double active_frac,
                                uint32_t* fuse_ctr, const input_gate_t* gate,
-                               uint32_t* done, uint32_t done_seq, bool skip_pip) {
+                               uint32_t* done, uint32_t done_seq, bool skip_pip,
+                               const batch_votes_t* votes) {
   // Pippenger batches under a skip list take the separate kernels only (launch_pip)
   if (skip_pip && (!skip_group_ok || fuse_ctr || gate || done)) return hipErrorInvalidValue;
+  // the comb phase's vote list: its callers' plain batches only (a vote's state says nothing
+  // about a keyed item, and the list's indices are 32 bits)
+  if (votes && (!skip_pip || skip_per_group != 1 || keys || active_frac < 1.0 ||
+                nitems > 0xffffffffull))
+    return hipErrorInvalidValue;
   // a gate is honoured by the fused head only: refuse it anywhere else (its waves would
   // read bytes the CPU has not written yet)
   if (gate && !verify_batch_gate_ok(nbatches, nitems)) return hipErrorInvalidValue;
@@ -2553,7 +2666,21 @@ hipError_t launch_verify_batch(const uint32_t* digests, const uint64_t* offsets,
     if (chunks)
       hipLaunchKernelGGL(k_bv_expand, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0,
                          stream, offsets, b, e - b, (uint32_t)chunks, w.chunk_start, w.chunks);
-    if (compact && chunks)
+    if (votes && chunks) {
+      // the chunks that hold a listed vote, dense; the others write the identity (no ladder)
+      hipError_t me = hipMemsetAsync(votes->nlive, 0, 4, stream);
+      if (me != hipSuccess) return me;
+      hipLaunchKernelGGL(k_bv_live_chunks, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0,
+                         stream, w.chunks, (uint32_t)chunks, w.chunk_start + (e - b),
+                         votes->state, w.outs, votes->live, votes->nlive);
+    }
+    if (votes) {
+      // the items of the listed votes: the grid is the host's bound, every vote of the call
+      if (chunks)
+        hipLaunchKernelGGL(k_bv_items_listed, dim3((unsigned)((nitems + 255) / 256)), dim3(256),
+                           0, stream, votes->list, votes->count, digests, offsets, b, e, i0, i1,
+                           pmin, pks, sigs, z16, zkey, w.items, w.tabs);
+    } else if (compact && chunks)
       hipLaunchKernelGGL(k_bv_items_chunked, dim3((unsigned)((chunks * C + 255) / 256)),
                          dim3(256), 0, stream, w.chunks, (uint32_t)chunks,
                          w.chunk_start + (e - b), C, digests, b, i0, pks, sigs, z16, zkey,
@@ -2566,13 +2693,20 @@ hipError_t launch_verify_batch(const uint32_t* digests, const uint64_t* offsets,
       const hipError_t pe = launch_pip(digests, offsets, b, e, i0, i1, pmin, npip, pmax, pks,
                                        sigs, z16, zkey, w, status, fail_index, nogrp, stream,
                                        own_ctr ? fuse_ctr : w.chunk_start, gate, done,
-                                       done_seq, sk, pip_count);
+                                       done_seq, sk, pip_count,
+                                       votes ? votes->state : nullptr);
       if (pe != hipSuccess) return pe;
     }
-    if (chunks)
-      hipLaunchKernelGGL(k_bv_chunks, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0,
+    if (chunks && votes)
+      hipLaunchKernelGGL(k_bv_chunks<true>, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0,
                          stream, w.chunks, (uint32_t)chunks, offsets, b, i0, w.items, w.tabs,
-                         kt.tabs, kt.ks, w.outs, status, fail_index, w.chunk_start + (e - b));
+                         kt.tabs, kt.ks, w.outs, status, fail_index, votes->nlive, votes->state,
+                         votes->live);
+    else if (chunks)
+      hipLaunchKernelGGL(k_bv_chunks<false>, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0,
+                         stream, w.chunks, (uint32_t)chunks, offsets, b, i0, w.items, w.tabs,
+                         kt.tabs, kt.ks, w.outs, status, fail_index, w.chunk_start + (e - b),
+                         nullptr, nullptr);
     if (multi)
       hipLaunchKernelGGL(k_bv_combine,
                          dim3((unsigned)std::min<uint64_t>(multi, kCombineMaxBlocks)), dim3(256),
@@ -3108,9 +3242,10 @@ hipError_t launch_cert_sgroups(const uint32_t* cert_digest, const uint64_t* cvo,
     if (chunks) {
       hipLaunchKernelGGL(k_bv_expand, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0,
                          stream, cvo, b, be - b, (uint32_t)chunks, w.chunk_start, w.chunks);
-      hipLaunchKernelGGL(k_bv_chunks, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0,
+      hipLaunchKernelGGL(k_bv_chunks<false>, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0,
                          stream, w.chunks, (uint32_t)chunks, cvo, b, i0, w.items, w.tabs,
-                         keys.tabs, keys.ks, w.outs, status, fail_index, w.chunk_start + (be - b));
+                         keys.tabs, keys.ks, w.outs, status, fail_index, w.chunk_start + (be - b),
+                         nullptr, nullptr);
     }
     if (multi)
       hipLaunchKernelGGL(k_bv_combine,

@@ -73,7 +73,7 @@ struct nw_job {
     size_t bytes;
   } outs[3];
   int nouts = 0;
-  // verify_batch under the registered signers: the call's four counters in the pinned buffer
+  // verify_batch under the registered signers: the call's six counters in the pinned buffer
   // (part of its D2H section), added to the process-wide sums when the outputs are delivered
   const uint64_t* bstats = nullptr;
   bool pending = false;   // device work queued, outputs not yet delivered
@@ -98,11 +98,13 @@ struct DevPool {
 };
 DevPool g_pool[kMaxDev];
 
-// nw_batch_signers_stats: votes passed, votes not passed, batches settled, batches sent on
-std::atomic<uint64_t> g_bstats[4];
+// nw_batch_signers_stats: votes passed, votes not passed, batches settled, batches sent on;
+// nw_batch_signers_vote_stats: votes of the batches sent on left out of their sums, votes run
+constexpr int kBstats = nw::kBatchSignersCounters;
+std::atomic<uint64_t> g_bstats[kBstats];
 void job_deliver_bstats(nw_job* j) {
   if (!j->bstats) return;
-  for (int c = 0; c < 4; ++c) g_bstats[c].fetch_add(j->bstats[c], std::memory_order_relaxed);
+  for (int c = 0; c < kBstats; ++c) g_bstats[c].fetch_add(j->bstats[c], std::memory_order_relaxed);
   j->bstats = nullptr;
 }
 
@@ -537,7 +539,9 @@ int submit_batch(int dev, const uint8_t* digests, const uint8_t* pks, const uint
   const size_t m = nitems ? nitems : 1;
   // Registered signers on the device (DESIGN.md 5 "Round 12"): every vote first takes the comb
   // check under its registered key, and the batches all of whose votes pass are settled before
-  // launch_verify_batch runs, which then skips them. The path needs the device's B comb; where
+  // launch_verify_batch runs, which then skips them; a batch that is sent on runs over the votes
+  // that did not pass only (DESIGN.md 5 "Round 14"; NW_BATCH_SIGNERS_VOTES=0, read per call:
+  // over all its votes, as in round 12). The path needs the device's B comb; where
   // that cannot be had (no memory) the call runs as without a registry and no error is left
   // behind. With nothing registered nothing here adds a launch, an event wait, a copy or a lock
   // (one atomic load).
@@ -564,7 +568,7 @@ int submit_batch(int dev, const uint8_t* digests, const uint8_t* pks, const uint
                o_st = o_z + (z16 ? a256(16 * m) : 0),
                o_fi = o_st + a256(4 * nbatches),
                o_dn = o_fi + a256(8 * nbatches),   // NW_BATCH_SPIN's done word
-               o_ct = o_dn + 256,                  // the comb phase's four counters
+               o_ct = o_dn + 256,                  // the comb phase's six counters
                o_ws = o_ct + (signers ? 256 : 0),
                o_sg = o_ws + a256(nw::batch_workspace_bytes(nbatches, nitems)),
                end = o_sg + (signers ? a256(nw::batch_signers_bytes(nbatches, nitems)) : 0);
@@ -658,6 +662,9 @@ int submit_batch(int dev, const uint8_t* digests, const uint8_t* pks, const uint
     // the comb phase under the registry's read lease, which covers these launches only; a
     // registry cleared since the look above leaves the counters zero and no skip list
     const uint32_t* batch_ok = nullptr;
+    // the votes' states and lists live in the job's own scratch: the lease need not cover them
+    nw::batch_votes_t votes{};
+    const bool leave_out = signers && nw::batch_signers_votes();
     if (signers) {
       unsigned long long* const ctr = reinterpret_cast<unsigned long long*>(j->dbuf + o_ct);
       nw::rt::SignersLease sl;
@@ -670,12 +677,13 @@ int submit_batch(int dev, const uint8_t* digests, const uint8_t* pks, const uint
             reinterpret_cast<const uint64_t*>(ibuf + o_off), nbatches,
             reinterpret_cast<const uint32_t*>(ibuf + o_pk),
             reinterpret_cast<const uint32_t*>(ibuf + o_sig), nitems, sg, bcomb, j->dbuf + o_sg,
-            ctr, &batch_ok, j->stream);
+            ctr, &batch_ok, j->stream, leave_out ? &votes : nullptr);
         const int rrc = sl.release();
         JOB_HIP(se, "verify_batch launch (registered signers)");
         if (rrc) return rrc;
       } else {
-        JOB_HIP(hipMemsetAsync(ctr, 0, 32, j->stream), "hipMemsetAsync (signers' counters)");
+        JOB_HIP(hipMemsetAsync(ctr, 0, 8 * kBstats, j->stream),
+                "hipMemsetAsync (signers' counters)");
       }
     }
     const hipError_t e = nw::launch_verify_batch(
@@ -686,7 +694,8 @@ int submit_batch(int dev, const uint8_t* digests, const uint8_t* pks, const uint
         z16 ? reinterpret_cast<const uint32_t*>(ibuf + o_z) : nullptr, key, j->dbuf + o_ws,
         reinterpret_cast<int32_t*>(obuf + o_st), reinterpret_cast<uint64_t*>(obuf + o_fi),
         j->stream, nullptr, batch_ok, batch_ok ? 1 : 0, 1.0, out_direct ? j->dfz : nullptr,
-        gate ? &gt : nullptr, done, dseq, batch_ok != nullptr);
+        gate ? &gt : nullptr, done, dseq, batch_ok != nullptr,
+        batch_ok && votes.state ? &votes : nullptr);
     if (e != hipSuccess && out_direct) j->dfz_dirty = true;   // the head may have run
     JOB_HIP(e, "verify_batch launch");
     return 0;
@@ -1868,6 +1877,14 @@ int nw_batch_signers_stats(uint64_t out[4]) {
   if (rc) return rc;
   if (!out) return set_err(NW_E_INVALID_ARG, "null pointer");
   for (int c = 0; c < 4; ++c) out[c] = g_bstats[c].load(std::memory_order_relaxed);
+  return 0;
+}
+
+int nw_batch_signers_vote_stats(uint64_t out[2]) {
+  const int rc = nw::rt::ensure_init();
+  if (rc) return rc;
+  if (!out) return set_err(NW_E_INVALID_ARG, "null pointer");
+  for (int c = 0; c < 2; ++c) out[c] = g_bstats[4 + c].load(std::memory_order_relaxed);
   return 0;
 }
 

@@ -264,6 +264,19 @@ bool verify_batch_gate_ok(uint64_t nbatches, uint64_t nitems);
 // then honour the list (launch_batch_signers' callers); a lone large batch takes the separate
 // kernels, never the fused launches, so fuse_ctr, gate and done must be null. Without it no batch
 // of a call with a skip list takes the Pippenger path (the certificate callers).
+// votes (optional; with skip_pip, skip_per_group = 1, no key tables): the comb phase's verdict
+// per vote (launch_batch_signers, DESIGN.md 5 "Round 14"). A vote whose state is kVotePass adds
+// nothing to the sum of its batch for any coefficient set and cannot fail a check that comes
+// before the sum, so a batch that is sent on runs over its other votes only, each at its own
+// position: the items are built from `list`, the Straus ladder runs over the chunks that hold
+// a listed vote, and in a Pippenger batch a passed vote is neutral and not decompressed.
+struct batch_votes_t {
+  const uint32_t* state;   // one word per vote of the call (nw_strict.hpp kVotePass ...)
+  const uint32_t* list;    // the votes whose state is not kVotePass, dense, in any order
+  const uint32_t* count;   // their number (device)
+  uint32_t* live;          // nitems words: a slice's chunks that hold a listed vote
+  uint32_t* nlive;         // their number (device; cleared per slice)
+};
 hipError_t launch_verify_batch(const uint32_t* digests, const uint64_t* offsets,
                                const uint64_t* host_offsets, uint64_t nbatches,
                                const uint32_t* pks, const uint32_t* sigs, uint64_t nitems,
@@ -275,24 +288,33 @@ hipError_t launch_verify_batch(const uint32_t* digests, const uint64_t* offsets,
                                uint32_t* fuse_ctr = nullptr,
                                const input_gate_t* gate = nullptr,
                                uint32_t* done = nullptr, uint32_t done_seq = 0,
-                               bool skip_pip = false);
+                               bool skip_pip = false,
+                               const batch_votes_t* votes = nullptr);
 // Signature::verify_batch under the registered signers (nw_kernels.hip, DESIGN.md 5 "Round 12"):
 // every vote of the call through the comb check under its registered key (sg.n != 0; bcomb: the
 // device's B comb), the parities in batched inversions; *batch_ok_out (in scratch, nbatches words)
 // = 1 for a batch all of whose votes passed, which is then Ok under verify_batch for every
 // coefficient set, 0 otherwise. Follow with launch_verify_batch(skip_group_ok = *batch_ok_out,
 // skip_per_group = 1, skip_pip = true). scratch: batch_signers_bytes(nbatches, nitems) of
-// device memory; counters: 4 device words of 64 bits (set here): votes passed, votes not passed,
-// batches settled, batches sent on. offsets: nbatches + 1 values from 0.
+// device memory; counters: 6 device words of 64 bits (set here): votes passed, votes not passed,
+// batches settled, batches sent on, then the votes of the batches sent on that are left out
+// of their sums and those that run in them. offsets: nbatches + 1 values from 0.
+// votes_out (optional): filled with the per-vote states and the dense list of the votes that
+// did not pass (one atomic per workgroup; the count stays on the device), to be handed to
+// launch_verify_batch, which then leaves the passed votes out. Null (NW_BATCH_SIGNERS_VOTES=0,
+// batch_signers_votes()): no list, every vote of a batch sent on runs, counter 4 stays 0.
 // batch_signers_min_votes(): the call size from which the path is taken (NW_BATCH_SIGNERS_MIN_VOTES,
 // default 1; NW_BATCH_SIGNERS=0: never), read per call.
+constexpr int kBatchSignersCounters = 6;
 size_t batch_signers_bytes(uint64_t nbatches, uint64_t nitems);
 uint64_t batch_signers_min_votes();
+bool batch_signers_votes();
 hipError_t launch_batch_signers(const uint32_t* digests, const uint64_t* offsets, uint64_t nbatches,
                                 const uint32_t* pks, const uint32_t* sigs, uint64_t nitems,
                                 const strict_signers_t& sg, const struct ge_niels_pad* bcomb,
                                 void* scratch, unsigned long long* counters,
-                                const uint32_t** batch_ok_out, hipStream_t stream);
+                                const uint32_t** batch_ok_out, hipStream_t stream,
+                                batch_votes_t* votes_out = nullptr);
 
 // Certificate::verify vote batches merged over groups of certificates (nw_batch.hip):
 // cert_group_size() = certificates per group, 0 when the merge does not apply;

@@ -1078,7 +1078,9 @@ __global__ __launch_bounds__(256) void k_votes_keyed_inv(const uint32_t* __restr
 //   k_batch_signers        one lane per vote
 //   k_batch_signers_inv    parities (keyed_inv_chunk); the state ends as kVotePass / kVoteFail
 //   k_batch_signers_count  votes passed / not passed, batches settled / sent on: block sums,
-//                          one atomic per counter and block
+//                          one atomic per counter and block; the votes of the batches sent on
+//                          (counters 4 and 5); with `list`, the dense list of the votes that
+//                          did not pass (a block's votes at a base from one atomic)
 __device__ __forceinline__ uint64_t vote_batch(const uint64_t* __restrict__ offsets,
                                                uint64_t nbatches, uint64_t v) {
   uint64_t lo = 0, hi = nbatches;   // the last b with offsets[b] <= v (empty batches before it)
@@ -1090,10 +1092,12 @@ __device__ __forceinline__ uint64_t vote_batch(const uint64_t* __restrict__ offs
 }
 __global__ __launch_bounds__(256) void k_batch_signers_init(uint64_t nbatches,
                                                             uint32_t* __restrict__ batch_ok,
-                                                            unsigned long long* __restrict__ ctr) {
+                                                            unsigned long long* __restrict__ ctr,
+                                                            uint32_t* __restrict__ nlist) {
   const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (b < nbatches) batch_ok[b] = 1u;
-  if (b < 4) ctr[b] = 0ull;
+  if (b < kBsCounters) ctr[b] = 0ull;
+  if (b == 0 && nlist) *nlist = 0u;
 }
 __global__ __launch_bounds__(256, NW_COMB_WAVES) void k_batch_signers(
     const uint32_t* __restrict__ digests, const uint64_t* __restrict__ offsets, uint64_t nbatches,
@@ -1134,22 +1138,54 @@ __global__ __launch_bounds__(256) void k_batch_signers_inv(const uint64_t* __res
 }
 __global__ __launch_bounds__(256) void k_batch_signers_count(
     uint64_t nv, const uint32_t* __restrict__ state, uint64_t nbatches,
-    const uint32_t* __restrict__ batch_ok, unsigned long long* __restrict__ ctr) {
+    const uint32_t* __restrict__ batch_ok, const uint64_t* __restrict__ offsets,
+    unsigned long long* __restrict__ ctr, uint32_t* __restrict__ list,
+    uint32_t* __restrict__ nlist) {
   __shared__ uint32_t s_sum[4][4];
+  __shared__ unsigned long long s_sent[4];
+  __shared__ uint32_t s_base;
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const bool v = i < nv, b = i < nbatches;
   const bool pass = v && state[i] == kVotePass, okb = b && batch_ok[i] != 0;
   const bool is[4] = {pass, v && !pass, okb, b && !okb};   // kBsVotesPassed .. kBsSentOn
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint64_t mfail = __ballot(is[1]);
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     const uint32_t n = (uint32_t)__builtin_popcountll(__ballot(is[c]));
-    if ((threadIdx.x & 63u) == 0) s_sum[threadIdx.x >> 6][c] = n;
+    if (lane == 0) s_sum[wv][c] = n;
   }
+  // the votes of the batches sent on (a wave's sum by xor shuffles)
+  unsigned long long sent = is[3] ? offsets[i + 1] - offsets[i] : 0ull;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) sent += __shfl_xor(sent, o);
+  if (lane == 0) s_sent[wv] = sent;
   __syncthreads();
+  const uint32_t nfail = s_sum[0][1] + s_sum[1][1] + s_sum[2][1] + s_sum[3][1];
   if (threadIdx.x < 4) {
     const uint32_t c = threadIdx.x;
     const uint32_t tot = s_sum[0][c] + s_sum[1][c] + s_sum[2][c] + s_sum[3][c];
     if (tot) atomicAdd(ctr + c, (unsigned long long)tot);
+  } else if (threadIdx.x == 4) {
+    // a vote that did not pass belongs to a batch sent on, so with the list the votes left
+    // out are those batches' votes less the ones not passed: the counter's final value is
+    // that difference whatever the order of the blocks' additions (mod 2^64)
+    const unsigned long long tot = s_sent[0] + s_sent[1] + s_sent[2] + s_sent[3];
+    if (list) {
+      if (tot != nfail) atomicAdd(ctr + kBsVotesLeftOut, tot - (unsigned long long)nfail);
+      if (nfail) atomicAdd(ctr + kBsVotesRun, (unsigned long long)nfail);
+    } else if (tot) {
+      atomicAdd(ctr + kBsVotesRun, tot);
+    }
+  } else if (threadIdx.x == 5 && list && nfail) {
+    s_base = atomicAdd(nlist, nfail);
+  }
+  if (!list || nfail == 0) return;   // uniform over the block
+  __syncthreads();
+  if (is[1]) {
+    uint32_t pos = s_base + (uint32_t)__builtin_popcountll(mfail & ((1ull << lane) - 1ull));
+    for (uint32_t w = 0; w < wv; ++w) pos += s_sum[w][1];
+    list[pos] = (uint32_t)i;
   }
 }
 
@@ -1933,9 +1969,16 @@ hipError_t launch_votes_keyed(const uint32_t* cert_digest, const uint64_t* cvo, 
   return hipGetLastError();
 }
 
-// Scratch of launch_batch_signers: 20 limb planes and the state word per vote, a word per batch.
+// Scratch of launch_batch_signers: 20 limb planes and the state word per vote, a word per batch;
+// then the list of the votes that did not pass, launch_verify_batch's list of live chunks
+// (a word per vote each) and the two lists' counts.
 size_t batch_signers_bytes(uint64_t nbatches, uint64_t nitems) {
-  return 4 * (21 * nitems + nbatches);
+  return 4 * (23 * nitems + nbatches + 2);
+}
+static_assert(kBatchSignersCounters == kBsCounters, "the counter block of a call");
+bool batch_signers_votes() {
+  const char* e = getenv("NW_BATCH_SIGNERS_VOTES");
+  return !(e && e[0] == '0');
 }
 uint64_t batch_signers_min_votes() {
   if (const char* e = getenv("NW_BATCH_SIGNERS"))
@@ -1947,13 +1990,17 @@ hipError_t launch_batch_signers(const uint32_t* digests, const uint64_t* offsets
                                 const uint32_t* pks, const uint32_t* sigs, uint64_t nitems,
                                 const strict_signers_t& sg, const ge_niels_pad* bcomb,
                                 void* scratch, unsigned long long* counters,
-                                const uint32_t** batch_ok_out, hipStream_t stream) {
+                                const uint32_t** batch_ok_out, hipStream_t stream,
+                                batch_votes_t* votes_out) {
   if (nbatches == 0 || sg.n == 0 || !sg.lam || !bcomb) return hipErrorInvalidValue;
+  if (nitems > 0xffffffffull) votes_out = nullptr;   // the list's entries are 32 bits
   uint32_t* const base = static_cast<uint32_t*>(scratch);
   const vote_planes_t vp{base, base + 20 * nitems, nitems, nullptr};
   uint32_t* const batch_ok = base + 21 * nitems;
+  uint32_t* const list = batch_ok + nbatches;
+  uint32_t* const nlist = list + 2 * nitems;
   hipLaunchKernelGGL(k_batch_signers_init, dim3(grid_for(nbatches, 256)), dim3(256), 0, stream,
-                     nbatches, batch_ok, counters);
+                     nbatches, batch_ok, counters, votes_out ? nlist : nullptr);
   if (nitems) {
     hipLaunchKernelGGL(k_batch_signers, dim3(grid_for(nitems, 256)), dim3(256), 0, stream, digests,
                        offsets, nbatches, pks, sigs, nitems, signers_view{sg.keys, sg.slots, sg.cap},
@@ -1968,7 +2015,9 @@ hipError_t launch_batch_signers(const uint32_t* digests, const uint64_t* offsets
                        offsets, nbatches, nitems, nchunks, batch_ok, vp);
   }
   hipLaunchKernelGGL(k_batch_signers_count, dim3(grid_for(std::max(nitems, nbatches), 256)),
-                     dim3(256), 0, stream, nitems, vp.state, nbatches, batch_ok, counters);
+                     dim3(256), 0, stream, nitems, vp.state, nbatches, batch_ok, offsets, counters,
+                     votes_out ? list : nullptr, nlist);
+  if (votes_out) *votes_out = batch_votes_t{vp.state, list, nlist, list + nitems, nlist + 1};
   *batch_ok_out = batch_ok;
   return hipGetLastError();
 }

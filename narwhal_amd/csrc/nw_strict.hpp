@@ -817,8 +817,10 @@ NW_HD uint32_t batch_signers_vote(const Src& src, const strict_consts& K, const 
   return keyed_vote_check(src, K, bc, tab_of(row), batch_signers_flags(ok[row], lam[row]), X, Z);
 }
 // The four counters of a call (nw_batch_signers_stats), from the votes' final states and the
-// batches' words.
-enum : int { kBsVotesPassed = 0, kBsVotesNot = 1, kBsSettled = 2, kBsSentOn = 3 };
+// batches' words, and the two of nw_batch_signers_vote_stats: the votes of the batches sent on
+// that are left out of their sums (state kVotePass) and those that run in them.
+enum : int { kBsVotesPassed = 0, kBsVotesNot = 1, kBsSettled = 2, kBsSentOn = 3,
+             kBsVotesLeftOut = 4, kBsVotesRun = 5, kBsCounters = 6 };
 
 // Keyed strict verification: A is a committee key with comb tables j * 2^(W t) A
 // (keytab_wide / keytab_lazy; affine niels), keyflags bit 0 = decoded, bit 1 = small
