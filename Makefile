@@ -100,6 +100,14 @@ keysetsan: tools/keyset_san
 tools/keyset_san: tools/hostcheck.hip $(HDRS)
 	$(HIPCC) --cuda-host-only -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -DKEYSET_SAN_MAIN -Iinclude $< -o $@
 
+# the lane function that hashes R || A || M for the strict launch over messages of any length
+# (nw_sha512.hpp sha512_hram_lane) compiled for the CPU under AddressSanitizer / UBSan, as a
+# stand-alone program (not part of `all`; tests/test_sha512_hram_cpu.py builds and runs it)
+CLANGXX ?= /opt/rocm/llvm/bin/clang++
+hramsan: tools/hram_lane_san
+tools/hram_lane_san: tools/hram_lane_san.cpp tools/hram_san/hip/hip_runtime.h $(CSRC)/nw_sha512.hpp $(CSRC)/nw_field.hpp
+	$(CLANGXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -Itools/hram_san -I$(CSRC) $< -o $@
+
 loadgen: tools/libnw_loadgen.so
 tools/libnw_loadgen.so: tools/nw_loadgen.cpp include/narwhal_amd.h $(LIB)
 	g++ -O2 -std=c++17 -fPIC -shared -Iinclude $< -o $@ -Lnarwhal_amd -lnarwhal_amd -Wl,-rpath,'$$ORIGIN/../narwhal_amd' -pthread
@@ -118,7 +126,7 @@ tools/ubench_valu: tools/ubench_valu.hip
 	$(HIPCC) --offload-arch=$(ARCH) -O3 $< -o $@
 
 clean:
-	rm -rf $(BUILD) $(LIB) tools/libnw_hostcheck.so tools/libnw_lpcheck.so tools/libnw_wirecheck.so tools/libnw_stagecheck.so tools/libnw_loadgen.so tools/service_stress tools/service_stress_tsan tools/wire_canon_san tools/stage_san tools/keyset_san
+	rm -rf $(BUILD) $(LIB) tools/libnw_hostcheck.so tools/libnw_lpcheck.so tools/libnw_wirecheck.so tools/libnw_stagecheck.so tools/libnw_loadgen.so tools/service_stress tools/service_stress_tsan tools/wire_canon_san tools/stage_san tools/keyset_san tools/hram_lane_san
 	$(MAKE) -s -C oracle clean
 
-.PHONY: all oracle hostcheck lpcheck wirecheck stagecheck wiresan stagesan keysetsan loadgen stress ubench clean
+.PHONY: all oracle hostcheck lpcheck wirecheck stagecheck wiresan stagesan keysetsan hramsan loadgen stress ubench clean

@@ -121,6 +121,27 @@ int nw_verify_strict_many(const uint8_t* digests, size_t digest_stride, const ui
                           const uint8_t* sigs, size_t n, int32_t* status_out,
                           uint8_t* bitmap_out);
 
+/* n strict verifications over messages of any length: ed25519_dalek's
+ * PublicKey::verify_strict(&[u8]). Message i is lengths[i] bytes at data + offsets[i], as in
+ * nw_sha512_digest32_many (any alignment, gaps and overlaps allowed; lengths is required; only
+ * the referenced bytes are read, nothing for an empty message). Statuses, bitmap and the order
+ * of the checks are exactly nw_verify_strict_many's, with k = SHA-512(R || A || M) mod l over
+ * the raw bytes: for 32-byte messages the two entries agree item by item. A kernel first
+ * computes every item's k, one lane per message (a wave runs as long as its longest message, so
+ * the entry is meant for messages of up to a few KB: transactions, not blobs), then the
+ * unkeyed strict launch runs unchanged over those k: the call's key set, the comb check of its
+ * hot keys, the registered signers (nw_strict_signers_set serves this entry as it serves
+ * nw_verify_strict_many), triage, ladder, bitmap and slices, under the same NW_TRIAGE_SLICE /
+ * NW_STRICT_KEYS / NW_STRICT_COMB* / NW_STRICT_SIGNERS_MIN_ITEMS knobs and counted by the same
+ * nw_dev_strict_*_stats. The entry always runs the two-pass launch: NW_STRICT_TRIAGE=0, the
+ * 32-byte launch's A/B hook, is not honoured here. The device keeps 32 bytes per item of the
+ * largest such call (NW_E_OUT_OF_MEMORY when it cannot; the library stays usable). n = 0 is Ok.
+ * Under nw_set_device(NW_ALL_DEVICES) each device gets one contiguous part of whole items. */
+int nw_verify_strict_msgs_many(const uint8_t* data, const uint64_t* offsets,
+                               const uint64_t* lengths, const uint8_t* pks,
+                               const uint8_t* sigs, size_t n, int32_t* status_out,
+                               uint8_t* bitmap_out);
+
 /* crypto::Signature::verify_batch(digest, votes) over n (pk, sig) pairs sharing one digest.
  * z16: optional n x 16-byte little-endian 128-bit coefficients (deterministic tests); NULL =
  * fresh coefficients from the OS CSPRNG (the reference draws them from thread_rng).
@@ -164,6 +185,12 @@ struct nw_certificates;
 int nw_submit_verify_strict(const uint8_t* digests, size_t digest_stride, const uint8_t* pks,
                             const uint8_t* sigs, size_t n, int32_t* status_out,
                             uint8_t* bitmap_out, nw_job** job);
+/* verify_strict over messages of any length (as nw_verify_strict_msgs_many; the referenced
+ * bytes are packed contiguously at submit). */
+int nw_submit_verify_strict_msgs(const uint8_t* data, const uint64_t* offsets,
+                                 const uint64_t* lengths, const uint8_t* pks,
+                                 const uint8_t* sigs, size_t n, int32_t* status_out,
+                                 uint8_t* bitmap_out, nw_job** job);
 /* Signature::verify_batch per batch (as nw_verify_batch_many; fail_index_out optional). */
 int nw_submit_verify_batch_many(const uint8_t* digests, const uint8_t* pks, const uint8_t* sigs,
                                 const uint64_t* offsets, size_t nbatches, const uint8_t* z16,
@@ -490,6 +517,14 @@ int nw_dev_verify_strict_many(const void* digests, size_t digest_stride, const v
                               const void* sigs, size_t n, int32_t* status_out,
                               void* bitmap_out, void* stream);
 
+/* Device form of nw_verify_strict_msgs_many: data, offsets, lengths, pks, sigs, status_out
+ * (n x int32) and bitmap_out (ceil(n / 64) x uint64) are device pointers; status_out and
+ * bitmap_out are required. The k of every item goes to a buffer of the library's own, ordered
+ * with the device's other strict launches (two launches on two streams do not overlap on it). */
+int nw_dev_verify_strict_msgs_many(const void* data, const uint64_t* offsets,
+                                   const uint64_t* lengths, const void* pks, const void* sigs,
+                                   size_t n, void* status_out, void* bitmap_out, void* stream);
+
 int nw_dev_keypair_from_seed_many(const void* seeds, size_t n, void* pks_out, void* stream);
 
 int nw_dev_sign_many(const void* sks, size_t sk_stride, const void* digests,
@@ -529,6 +564,9 @@ int nw_dev_certificates_verify_many(const nw_committee* committee, const nw_cert
  * device. Return 0, or a negative NW_E_* (the verdicts go to status_out / index_out). */
 int nw_host_verify_strict_many(const uint8_t* msgs, size_t msg_stride, const uint8_t* pks,
                                const uint8_t* sigs, size_t n, int32_t* status_out);
+int nw_host_verify_strict_msgs_many(const uint8_t* data, const uint64_t* offsets,
+                                    const uint64_t* lengths, const uint8_t* pks,
+                                    const uint8_t* sigs, size_t n, int32_t* status_out);
 int nw_host_verify_batch_many(const uint8_t* digests, const uint8_t* pks, const uint8_t* sigs,
                               const uint64_t* offsets, size_t nbatches, const uint8_t* z16,
                               int32_t* status_out, uint64_t* fail_index_out);

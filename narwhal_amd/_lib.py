@@ -44,22 +44,20 @@ def header_symbols() -> list[str]:
     return sorted(set(re.findall(r"\b(nw_[a-z0-9_]+)\s*\(", txt)))
 
 
-def lib() -> ctypes.CDLL:
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise EngineError(f"{LIB_PATH} not built (run `make` at the repo root); "
-                          "narwhal_amd has no CPU fallback")
-    L = ctypes.CDLL(LIB_PATH)
+def prototypes() -> dict:
+    """name -> (argument types, result type) of every entry point lib() declares."""
     P, S, I = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
-    sig = {
+    return {
         "nw_init": ([], I), "nw_device_count": ([], I), "nw_set_device": ([I], I),
         "nw_get_device": ([], I), "nw_last_error": ([], ctypes.c_char_p),
         "nw_version": ([], ctypes.c_char_p), "nw_synchronize": ([], I), "nw_prepare": ([], I),
         "nw_sha512_digest32_many": ([P, P, P, S, P], I),
         "nw_signature_verify": ([P, P, P], I),
         "nw_verify_strict_many": ([P, S, P, P, S, P, P], I),
+        "nw_verify_strict_msgs_many": ([P, P, P, P, P, S, P, P], I),
+        "nw_submit_verify_strict_msgs": ([P, P, P, P, P, S, P, P, ctypes.POINTER(P)], I),
+        "nw_dev_verify_strict_msgs_many": ([P, P, P, P, P, S, P, P, P], I),
+        "nw_host_verify_strict_msgs_many": ([P, P, P, P, P, S, P], I),
         "nw_signature_verify_batch": ([P, P, P, S, P, ctypes.POINTER(S)], I),
         "nw_verify_batch_many": ([P, P, P, P, S, P, P], I),
         "nw_dev_sha512_digest32_many": ([P, P, P, S, P, P], I),
@@ -111,7 +109,17 @@ def lib() -> ctypes.CDLL:
         "nw_host_certificates_verify_many": ([P, P, P, I, P, P], I),
         "nw_host_votes_verify_many": ([P, P, P, P, P, P, S, P], I),
     }
-    for name, (args, res) in sig.items():
+
+
+def lib() -> ctypes.CDLL:
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise EngineError(f"{LIB_PATH} not built (run `make` at the repo root); "
+                          "narwhal_amd has no CPU fallback")
+    L = ctypes.CDLL(LIB_PATH)
+    for name, (args, res) in prototypes().items():
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = res

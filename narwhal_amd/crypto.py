@@ -9,11 +9,13 @@ behaviour, so code (and tests) written against the Rust crate read the same here
     Signature(part1, part2), flatten      lib.rs:177-198
     Signature.verify(digest, pk)          lib.rs:200-204  -> raises CryptoError
     Signature.verify_batch(digest, votes) lib.rs:206-219  -> raises CryptoError
+    Signature.verify_message(msg, pk)     dalek's verify_strict(&[u8]): a message of any length
     CryptoError                           lib.rs:18 (ed25519::Error, opaque)
 
 Every check runs in the gfx950 kernels through the C ABI (include/narwhal_amd.h); there
 is no CPU path. Runtime/device failures raise EngineError, never CryptoError.
-Bulk helpers (verify_strict_many, verify_batch_many, sha512_digest32_many) expose the
+Bulk helpers (verify_strict_many, verify_strict_msgs_many, verify_batch_many,
+sha512_digest32_many) expose the
 batched entry points the aggregation service uses.
 """
 from __future__ import annotations
@@ -31,6 +33,7 @@ from ._lib import EngineError, check
 __all__ = ["Digest", "Hash", "PublicKey", "SecretKey", "Signature", "CryptoError",
            "EngineError", "generate_keypair", "keypair_from_seed_many", "sign_many",
            "sha512_digest", "sha512_digest32_many", "verify_strict_many",
+           "verify_strict_msgs_many",
            "verify_batch_many", "set_strict_signers", "strict_signers_count",
            "strict_signers_stats", "batch_signers_stats",
            "batch_signers_vote_stats"]
@@ -184,6 +187,14 @@ class Signature:
         if rc != _lib.NW_OK:
             raise CryptoError(rc)
 
+    def verify_message(self, message: bytes, public_key: PublicKey) -> None:
+        """ed25519_dalek's PublicKey::verify_strict(message, signature) over the message's own
+        bytes, of any length (Signature.verify is the same check of a 32-byte Digest)."""
+        st, _ = verify_strict_msgs_many([bytes(message)], np.frombuffer(public_key.value, np.uint8),
+                                        np.frombuffer(self.flatten(), np.uint8))
+        if st[0] != _lib.NW_OK:
+            raise CryptoError(int(st[0]))
+
     @staticmethod
     def verify_batch(digest: Digest, votes: Iterable[tuple[PublicKey, "Signature"]],
                      z16: bytes | None = None) -> None:
@@ -242,6 +253,43 @@ def verify_strict_many(digests: np.ndarray, pks: np.ndarray, sigs: np.ndarray,
         check(_lib.lib().nw_verify_strict_many(_ptr(digests), 0 if shared_digest else 32,
                                                _ptr(pks), _ptr(sigs), n, _ptr(st), _ptr(bm)),
               "nw_verify_strict_many")
+    return st, bm
+
+
+def verify_strict_msgs_many(messages, pks: np.ndarray,
+                            sigs: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """Bulk verify_strict over messages of any length (nw_verify_strict_msgs_many). ``messages``
+    is a list of bytes, or the (data, offsets, lengths) arrays of nw_sha512_digest32_many:
+    message i is lengths[i] bytes at data[offsets[i]:]. Returns (status int32[n], bitmap
+    uint8[ceil(n/8)]) like verify_strict_many."""
+    if isinstance(messages, tuple):
+        data, offsets, lengths = messages
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lengths = np.ascontiguousarray(lengths, dtype=np.uint64)
+    else:
+        raw = [bytes(m) for m in messages]
+        lengths = np.array([len(m) for m in raw], dtype=np.uint64)
+        offsets = np.zeros(len(raw), dtype=np.uint64)
+        if len(raw) > 1:
+            offsets[1:] = np.cumsum(lengths)[:-1]
+        data = np.frombuffer(b"".join(raw), np.uint8)
+    if data.size == 0:
+        data = np.zeros(1, np.uint8)
+    pks = np.ascontiguousarray(pks, dtype=np.uint8).reshape(-1, 32)
+    sigs = np.ascontiguousarray(sigs, dtype=np.uint8).reshape(-1, 64)
+    n = pks.shape[0]
+    if len(offsets) != n or len(lengths) != n or sigs.shape[0] != n:
+        raise ValueError("messages, pks and sigs must name the same number of items")
+    filled = lengths > 0
+    if filled.any() and int((offsets[filled] + lengths[filled]).max()) > data.size:
+        raise ValueError("a message lies outside data")
+    st = np.zeros(n, dtype=np.int32)
+    bm = np.zeros((n + 7) // 8, dtype=np.uint8)
+    if n:
+        check(_lib.lib().nw_verify_strict_msgs_many(_ptr(data), _ptr(offsets), _ptr(lengths),
+                                                    _ptr(pks), _ptr(sigs), n, _ptr(st), _ptr(bm)),
+              "nw_verify_strict_msgs_many")
     return st, bm
 
 

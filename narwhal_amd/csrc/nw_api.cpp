@@ -48,6 +48,8 @@ struct SharedDev {
   uint64_t triage_keys = 0;    // key-set slots the region holds (nw::strict_keys_slots)
   void* comb_ws = nullptr;     // the hot keys' comb tables (grow-only, nw::strict_comb_bytes)
   uint64_t comb_slice = 0, comb_slots = 0, comb_keys = 0;   // what it was sized for
+  void* kplane = nullptr;      // k of every item of a launch over messages of any length
+  uint64_t kplane_cap = 0;     // items (32 bytes each; grow-only)
   nw::strict_signers_t signers;   // the registered signers: an allocation of their own, which
                                   // no growth of the triage or comb regions touches
   void* ktabs = nullptr;       // committee key tables (grow-only)
@@ -292,6 +294,30 @@ int nw_dev_verify_strict_many(const void* digests, size_t digest_stride, const v
                                   static_cast<const uint32_t*>(sigs), n, status_out,
                                   static_cast<uint64_t*>(bitmap_out), ws, s),
          "k_verify_strict launch");
+  return lease.release();
+}
+
+int nw_dev_verify_strict_msgs_many(const void* data, const uint64_t* offsets,
+                                   const uint64_t* lengths, const void* pks, const void* sigs,
+                                   size_t n, void* status_out, void* bitmap_out, void* stream) {
+  DevCtx* c;
+  int rc = begin(&c);
+  if (rc) return rc;
+  if (n == 0) return 0;
+  if (!data || !offsets || !lengths || !pks || !sigs || !status_out || !bitmap_out)
+    return set_err(NW_E_INVALID_ARG, "null pointer (status_out and bitmap_out are required)");
+  const hipStream_t s = pick_stream(stream, c);
+  nw::rt::Lease lease;
+  nw::strict_ws_t ws;
+  rc = lease.acquire(t_state.device, s);
+  if (!rc) rc = lease.strict_ws(&ws, n, true);
+  if (rc) return rc;
+  NW_HIP(nw::launch_verify_strict_msgs(static_cast<const uint8_t*>(data), offsets, lengths,
+                                       static_cast<const uint32_t*>(pks),
+                                       static_cast<const uint32_t*>(sigs), n,
+                                       static_cast<int32_t*>(status_out),
+                                       static_cast<uint64_t*>(bitmap_out), ws, s),
+         "strict launch over messages");
   return lease.release();
 }
 
@@ -1198,7 +1224,7 @@ int SignersLease::release() {
   return reader_release(g_shared[dev_], stream_, "signers lease: hipEventRecord");
 }
 
-int Lease::strict_ws(nw::strict_ws_t* out, size_t n) {
+int Lease::strict_ws(nw::strict_ws_t* out, size_t n, bool msgs) {
   SharedDev& d = g_shared[dev_];
   if (!d.strict_ws) {
     hipError_t e = nw::table_malloc(&d.strict_ws, nw::strict_workspace_bytes());
@@ -1208,7 +1234,25 @@ int Lease::strict_ws(nw::strict_ws_t* out, size_t n) {
     }
   }
   // the launch's plan (its knobs, read here once per launch)
-  nw::strict_launch_plan_t p = nw::strict_launch_plan(n, d.signers.n);
+  nw::strict_launch_plan_t p = nw::strict_launch_plan(n, d.signers.n, msgs);
+  // the k plane of a launch over messages: grown after every queued launch that uses the old
+  // one has finished (they are all ordered before d.last)
+  if (msgs && n > d.kplane_cap) {
+    if (d.kplane) {
+      if (d.last_valid) (void)hipEventSynchronize(d.last);
+      (void)hipFree(d.kplane);
+      d.kplane = nullptr;
+      d.kplane_cap = 0;
+    }
+    const uint64_t cap = std::max<uint64_t>(n + n / 4, 4096);
+    hipError_t e = hipMalloc(&d.kplane, 32 * cap);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      d.kplane = nullptr;
+      return ::set_err(NW_E_OUT_OF_MEMORY, "hipMalloc (strict k plane)", e);
+    }
+    d.kplane_cap = cap;
+  }
   // the two-pass path's slice: grown (at least doubled, up to the slice limit's size) after
   // every queued launch that uses the old one has finished; the key set's tables follow the
   // planes in the same region, which also grows when a launch asks for more slots
@@ -1260,7 +1304,8 @@ int Lease::strict_ws(nw::strict_ws_t* out, size_t n) {
   }
   *out = nw::strict_ws_t{d.strict_ws, d.triage_ws, p.comb() ? d.comb_ws : nullptr,
                          {d.triage_cap, d.triage_keys, d.comb_keys}, p,
-                         p.signers ? d.signers : nw::strict_signers_t{}};
+                         p.signers ? d.signers : nw::strict_signers_t{},
+                         msgs ? static_cast<uint32_t*>(d.kplane) : nullptr};
   return 0;
 }
 

@@ -368,9 +368,14 @@ void committee_free(Committee* c) { delete c; }
 // Signatures
 // ---------------------------------------------------------------------------------------
 int verify_strict(const uint8_t msg32[32], const uint8_t pk[32], const uint8_t sig[64]) {
+  return verify_strict_msg(msg32, 32, pk, sig);
+}
+
+int verify_strict_msg(const uint8_t* msg, size_t len, const uint8_t pk[32],
+                      const uint8_t sig[64]) {
   const Consts& C = consts();
   sc k;
-  hram(k, sig, pk, msg32, 32);
+  hram(k, sig, pk, msg, len);
   uint32_t Aw[8], Rw[8], Sw[8];
   load8(Aw, pk);
   load8(Rw, sig);
@@ -670,6 +675,17 @@ int nw_host_verify_strict_many(const uint8_t* msgs, size_t msg_stride, const uin
   if (n && (!msgs || !pks || !sigs || !status_out)) return NW_E_INVALID_ARG;
   for (size_t i = 0; i < n; ++i)
     status_out[i] = nw::host::verify_strict(msgs + msg_stride * i, pks + 32 * i, sigs + 64 * i);
+  return 0;
+}
+
+int nw_host_verify_strict_msgs_many(const uint8_t* data, const uint64_t* offsets,
+                                    const uint64_t* lengths, const uint8_t* pks,
+                                    const uint8_t* sigs, size_t n, int32_t* status_out) {
+  if (n && (!data || !offsets || !lengths || !pks || !sigs || !status_out))
+    return NW_E_INVALID_ARG;
+  for (size_t i = 0; i < n; ++i)
+    status_out[i] = nw::host::verify_strict_msg(data + offsets[i], (size_t)lengths[i],
+                                                pks + 32 * i, sigs + 64 * i);
   return 0;
 }
 

@@ -27,6 +27,9 @@ void committee_free(Committee* c);
 // crypto::Signature::verify (crypto/src/lib.rs:200-204) of a 32-byte digest: NW_OK or the
 // NW_ERR_* of the first failing check (the kernels' strict ladder, nw_strict.hpp).
 int verify_strict(const uint8_t msg32[32], const uint8_t pk[32], const uint8_t sig[64]);
+// The same over a message of any length (dalek's verify_strict(&[u8])): only k's hash input differs.
+int verify_strict_msg(const uint8_t* msg, size_t len, const uint8_t pk[32],
+                      const uint8_t sig[64]);
 // crypto::Signature::verify_batch (crypto/src/lib.rs:206-219): status, *fail_index (item or
 // n for the equation). z16: n x 16-byte coefficients, or nullptr for ChaCha20 keyed from the
 // OS CSPRNG. com (optional): votes whose key is a committee member take the keyed check.

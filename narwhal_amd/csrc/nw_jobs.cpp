@@ -778,6 +778,68 @@ int submit_sha(int dev, const uint8_t* data, const uint64_t* offsets, const uint
   return 0;
 }
 
+// Strict verification over messages of any length: the referenced bytes packed contiguously as
+// submit_sha does, keys and signatures staged as submit_strict does; the k plane is the
+// device's, under the lease.
+int submit_strict_msgs(int dev, const uint8_t* data, const uint64_t* offsets,
+                       const uint64_t* lengths, const uint8_t* pks, const uint8_t* sigs, size_t n,
+                       int32_t* status_out, uint8_t* bitmap_out, nw_job** job) {
+  nw_job* j;
+  int rc = job_acquire(dev, &j);
+  if (rc) return rc;
+  if (n == 0) {
+    *job = j;
+    return 0;
+  }
+  uint64_t total = 0;
+  for (size_t i = 0; i < n; ++i) total += lengths[i];
+  const size_t o_data = 0, o_off = a256(total ? total : 1), o_len = o_off + a256(8 * n),
+               o_pk = o_len + a256(8 * n), o_sig = o_pk + a256(32 * n),
+               o_st = o_sig + a256(64 * n), o_bm = o_st + a256(4 * n),
+               end = o_bm + a256(8 * ((n + 63) / 64));
+  rc = job_reserve(j, end, end);
+  if (rc) return job_abort(j, rc);
+  uint64_t* offs = reinterpret_cast<uint64_t*>(j->hbuf + o_off);
+  uint64_t pos = 0;
+  for (size_t i = 0; i < n; ++i) {
+    offs[i] = pos;
+    pos += lengths[i];
+  }
+  size_t i = 0;
+  while (i < n) {   // contiguous runs are copied in one go
+    size_t k = i + 1;
+    while (k < n && offsets[k] == offsets[k - 1] + lengths[k - 1]) ++k;
+    const uint64_t bytes = offs[k - 1] + lengths[k - 1] - offs[i];
+    if (bytes) memcpy(j->hbuf + o_data + offs[i], data + offsets[i], bytes);
+    i = k;
+  }
+  memcpy(j->hbuf + o_len, lengths, 8 * n);
+  memcpy(j->hbuf + o_pk, pks, 32 * n);
+  memcpy(j->hbuf + o_sig, sigs, 64 * n);
+  rc = job_run(j, o_st, o_st, end - o_st, [&]() -> int {
+    nw::rt::Lease lease;
+    nw::strict_ws_t ws;
+    int lrc = lease.acquire(j->dev, j->stream);
+    if (!lrc) lrc = lease.strict_ws(&ws, n, true);
+    if (lrc) return lrc;
+    JOB_HIP(nw::launch_verify_strict_msgs(reinterpret_cast<const uint8_t*>(j->dbuf + o_data),
+                                          reinterpret_cast<const uint64_t*>(j->dbuf + o_off),
+                                          reinterpret_cast<const uint64_t*>(j->dbuf + o_len),
+                                          reinterpret_cast<const uint32_t*>(j->dbuf + o_pk),
+                                          reinterpret_cast<const uint32_t*>(j->dbuf + o_sig), n,
+                                          reinterpret_cast<int32_t*>(j->dbuf + o_st),
+                                          reinterpret_cast<uint64_t*>(j->dbuf + o_bm), ws,
+                                          j->stream),
+            "strict launch over messages");
+    return lease.release();
+  });
+  if (rc) return job_abort(j, rc);
+  job_out(j, status_out, o_st, 4 * n);
+  job_out(j, bitmap_out, o_bm, (n + 7) / 8);
+  *job = j;
+  return 0;
+}
+
 // ---- primary messages ------------------------------------------------------------------
 // The sections of a job's staging buffers (pinned and device share one layout): nw_stage.hpp
 // states the committee's, the header stream's, the certificate votes' and the Vote messages';
@@ -1545,6 +1607,33 @@ int nw_submit_verify_strict(const uint8_t* digests, size_t digest_stride, const 
   return submit_entry(job, check, one, many);
 }
 
+int nw_submit_verify_strict_msgs(const uint8_t* data, const uint64_t* offsets,
+                                 const uint64_t* lengths, const uint8_t* pks, const uint8_t* sigs,
+                                 size_t n, int32_t* status_out, uint8_t* bitmap_out,
+                                 nw_job** job) {
+  const auto check = [&] {
+    const bool bad = n && (!data || !offsets || !lengths || !pks || !sigs);
+    return bad ? set_err(NW_E_INVALID_ARG, "null pointer") : 0;
+  };
+  const auto one = [&](int dev) {
+    return submit_strict_msgs(dev, data, offsets, lengths, pks, sigs, n, status_out, bitmap_out,
+                              job);
+  };
+  const auto many = [&](const std::vector<int>& devs) {
+    // whole items per part, each with its own slice of the offsets (64-item boundaries: the
+    // bitmap's bytes)
+    return fan_out(devs, even_bounds(n, devs.size(), 64),
+                   [&](int dev, size_t a, size_t e, nw_job** sub) {
+                     return submit_strict_msgs(dev, data, offsets + a, lengths + a, pks + 32 * a,
+                                               sigs + 64 * a, e - a,
+                                               status_out ? status_out + a : nullptr,
+                                               bitmap_out ? bitmap_out + a / 8 : nullptr, sub);
+                   },
+                   job);
+  };
+  return submit_entry(job, check, one, many);
+}
+
 int nw_submit_verify_batch_many(const uint8_t* digests, const uint8_t* pks, const uint8_t* sigs,
                                 const uint64_t* offsets, size_t nbatches, const uint8_t* z16,
                                 int32_t* status_out, uint64_t* fail_index_out, nw_job** job) {
@@ -1920,6 +2009,14 @@ int nw_verify_strict_many(const uint8_t* digests, size_t digest_stride, const ui
   return run_blocking(nw_submit_verify_strict(digests, digest_stride, pks, sigs, n, status_out,
                                               bitmap_out, &j),
                       j);
+}
+
+int nw_verify_strict_msgs_many(const uint8_t* data, const uint64_t* offsets,
+                               const uint64_t* lengths, const uint8_t* pks, const uint8_t* sigs,
+                               size_t n, int32_t* status_out, uint8_t* bitmap_out) {
+  nw_job* j = nullptr;
+  return run_blocking(nw_submit_verify_strict_msgs(data, offsets, lengths, pks, sigs, n,
+                                                   status_out, bitmap_out, &j), j);
 }
 
 int nw_signature_verify(const uint8_t sig[64], const uint8_t digest[32], const uint8_t pk[32]) {

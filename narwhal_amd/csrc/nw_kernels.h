@@ -38,7 +38,7 @@ size_t strict_workspace_bytes();
 // strict_triage_slice(n) = min(slice limit, n rounded up to 64); the limit is 2^24 items
 // (NW_TRIAGE_SLICE = items lowers it, e.g. to run a small input through several slices);
 // 0 when the two-pass path is off.
-uint64_t strict_triage_slice(uint64_t n);
+uint64_t strict_triage_slice(uint64_t n, bool always = false);
 // The slice's key set: the items of a slice share public keys, so each distinct key is
 // decompressed and tabulated once per slice into a table that lives for the call only.
 // strict_keys_slots(slice) = slots of its hash table for a slice of that many items, from
@@ -108,7 +108,8 @@ struct strict_launch_plan_t {
   // the comb path runs: with registered signers even without room for a call-local table
   bool comb() const { return hot_cap != 0 || signers; }
 };
-strict_launch_plan_t strict_launch_plan(uint64_t n, uint32_t registered);
+// always: plan the two-pass launch whatever NW_STRICT_TRIAGE says (launch_verify_strict_msgs).
+strict_launch_plan_t strict_launch_plan(uint64_t n, uint32_t registered, bool always = false);
 // What Lease::strict_ws hands a launch: the allocations, what they hold and the launch's plan.
 struct strict_caps_t {
   uint64_t slice = 0, key_slots = 0;   // triage: strict_triage_bytes(slice, key_slots)
@@ -121,6 +122,7 @@ struct strict_ws_t {
   strict_caps_t caps;
   strict_launch_plan_t plan;  // without comb: hot_cap = 0 and signers = false
   strict_signers_t signers;   // the device's registered signers when plan.signers (else n == 0)
+  uint32_t* kplane = nullptr; // launch_verify_strict_msgs only: 8 words per item of the call
 };
 // The comb check for a call's hot keys (DESIGN.md 5 "Round 9"): a key of the slice's set used
 // by at least NW_STRICT_COMB_MIN items (default 256) that decodes and is not small gets 8-bit
@@ -152,6 +154,20 @@ hipError_t launch_verify_strict(const uint32_t* msgs, uint32_t msg_stride_words,
                                 const uint32_t* pks, const uint32_t* sigs, uint64_t n,
                                 int32_t* status, uint64_t* bitmap, const strict_ws_t& workspace,
                                 hipStream_t stream, const struct key_tables_t* keys = nullptr);
+
+// The same over messages of any length (Ed25519 verify_strict over &[u8]): message i is lengths[i]
+// bytes at data + offsets[i] (device arrays; any alignment). k_strict_hram writes k = SHA-512(R ||
+// A || M) mod l of every item into workspace.kplane (the library's: 32 bytes per item, stride 8
+// words, the shape of a digests array), then the unkeyed two-pass launch runs over the plane with
+// the instances of its kernels that read k instead of hashing 32 bytes: key set, call-local
+// comb, registered signers, to-do list, triage with decided items, ladder, bitmap and slices,
+// under the same knobs and counted by the same statistics. Always two passes: NW_STRICT_TRIAGE=0
+// is not honoured (workspace.plan comes from strict_launch_plan(n, registered, true)).
+hipError_t launch_verify_strict_msgs(const uint8_t* data, const uint64_t* offsets,
+                                     const uint64_t* lengths, const uint32_t* pks,
+                                     const uint32_t* sigs, uint64_t n, int32_t* status,
+                                     uint64_t* bitmap, const strict_ws_t& workspace,
+                                     hipStream_t stream);
 
 hipError_t launch_keypair(const uint32_t* seeds, uint64_t n, uint32_t* pks, hipStream_t stream);
 

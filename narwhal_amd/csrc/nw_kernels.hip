@@ -159,6 +159,66 @@ struct strict_src_global {
   }
 };
 
+// The same inputs with k already computed (launch_verify_strict_msgs: k_strict_hram hashed
+// R || A || M for a message of any length and reduced it): K() is eight loads from the item's
+// row of the k plane, no hash and no reduction. The instances over this source are kernels of
+// their own (k_strict_triage_k, k_strict_keyed_hot_k, k_strict_keyed_signers_k), so those over
+// strict_src_global keep their code objects.
+struct strict_src_plane {
+  static constexpr bool kPre = false;
+  static constexpr bool kScalars = false;
+  static constexpr bool kSharedA = false;
+  const uint32_t* pk;    // 8 words
+  const uint32_t* sig;   // 16 words: R || s
+  const uint32_t* k;     // 8 words: SHA-512(R || A || M) mod l
+  __device__ void A(uint32_t w[8]) const {
+    const uint32_t* p = opaque_ptr(pk);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) w[j] = p[j];
+  }
+  __device__ void R(uint32_t w[8]) const {
+    const uint32_t* p = opaque_ptr(sig);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) w[j] = p[j];
+  }
+  __device__ void S(uint32_t w[8]) const {
+    const uint32_t* p = opaque_ptr(sig);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) w[j] = p[8 + j];
+  }
+  __device__ void K(uint32_t kw[8]) const {
+    const uint32_t* p = opaque_ptr(k);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) kw[j] = p[j];
+  }
+};
+
+// k of every item of a strict launch over messages of any length (launch_verify_strict_msgs):
+// one lane per item hashes R || A || M (sha512_hram_lane, nw_sha512.hpp: message i is lengths[i]
+// bytes at data + offsets[i], any alignment), reduces mod l and writes the 8 words at
+// kplane + 8 i, the shape of the 32-byte launch's digests array. A wave runs as long as its
+// longest message.
+__global__ __launch_bounds__(256) void k_strict_hram(const uint8_t* __restrict__ data,
+                                                     const uint64_t* __restrict__ offsets,
+                                                     const uint64_t* __restrict__ lengths,
+                                                     const uint32_t* __restrict__ pks,
+                                                     const uint32_t* __restrict__ sigs, uint64_t n,
+                                                     uint32_t* __restrict__ kplane) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t Rw[8], Aw[8], hx[16];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    Rw[j] = sigs[16 * i + j];
+    Aw[j] = pks[8 * i + j];
+  }
+  sha512_hram_lane(hx, Rw, Aw, data + offsets[i], lengths[i]);
+  sc k;
+  sc_reduce512(k, hx);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) kplane[8 * i + j] = k.w[j];
+}
+
 // The same inputs with A's and R's x already decompressed (k_strict_triage): x limb k of
 // point pt (0 = A, 1 = R) of survivor q at xs[(10 pt + k) cap + q]. y is the encoding's own
 // (fe_frombytes), Z = 1, T = x y: exactly the point ge_frombytes returned. The same pass also
@@ -371,76 +431,14 @@ __global__ __launch_bounds__(256, NW_STRICT_WAVES) void k_verify_strict(const ui
 #ifndef NW_TRIAGE_WAVES
 #define NW_TRIAGE_WAVES 4   // waves per SIMD (129 VGPRs unbounded: 3)
 #endif
-__global__ __launch_bounds__(256, NW_TRIAGE_WAVES) void k_strict_triage(
-    const uint32_t* __restrict__ msgs, uint32_t msg_stride_words, const uint32_t* __restrict__ pks,
-    const uint32_t* __restrict__ sigs, uint64_t i0, uint64_t ns, int32_t* __restrict__ status,
-    uint32_t* __restrict__ xs, uint64_t cap, uint32_t* __restrict__ list,
-    uint32_t* __restrict__ count, const uint32_t* __restrict__ keyslot,
-    const uint32_t* __restrict__ kflags, const uint32_t* __restrict__ todo,
-    const uint32_t* __restrict__ todo_count, unsigned long long* __restrict__ todo_total,
-    const uint32_t* __restrict__ nhot, unsigned long long* __restrict__ settled) {
-  // todo == nullptr, or no hot key in the slice (*nhot == 0: the comb kernels did nothing):
-  // lane q takes item q of the slice; else the item of entry todo[q], q < *todo_count (the items
-  // the comb check did not pass, k_strict_todo_list). An entry with kTodoDecided set is an item
-  // whose comb sum ran and gave R' != decode(R): its status is the triage's own if the triage
-  // rejects it (R does not decode), else NW_ERR_EQUATION (comb_settled_status); either way it is
-  // settled here and never reaches the ladder. settled[wave & (kCombStatLanes - 1)] += the
-  // wave's items settled as equation failures (diagnostics, one atomic per wave that has any).
-  const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (todo && *nhot == 0) todo = nullptr;
-  const uint64_t nq = todo ? (uint64_t)*todo_count : ns;
-  const bool active = q < nq;
-  // *todo_total += the slice's items that come here (diagnostics, kept over a launch's slices)
-  if (todo_total && q == 0) atomicAdd(todo_total, (unsigned long long)nq);
-  if (__ballot(active) == 0) return;
-  const uint32_t entry = todo ? todo[active ? q : 0] : (uint32_t)q;
-  const bool decided = todo && (entry & kTodoDecided) != 0;
-  const uint64_t j = todo ? (uint64_t)comb_todo_item(entry) : q;
-  const uint64_t i = i0 + (active ? j : 0);
-  const strict_src_global src{pks + 8 * i, sigs + 16 * i, msgs + (uint64_t)msg_stride_words * i};
-  // the key's slot in the slice's set (keyslot == nullptr: the set is off); an idle lane of the
-  // last wave takes item i0's
-  const uint32_t slot = keyslot ? keyslot[active ? j : 0] : kNoSlot;
-  const uint32_t keyflags = slot != kNoSlot ? kflags[slot] : kNoSlot;
-  fe xa, xr;
-  const int st = strict_triage(src, g_consts.sk, xa, xr, keyflags,
-                               [](bool b) { return __ballot(b) != 0; });
-  // (comb_settled_status of a rejected item is the triage's status, decided or not)
-  if (active && (st != NW_OK || decided)) status[i] = comb_settled_status(st);
-  const uint32_t lane = threadIdx.x & 63u;
-  if (todo) {
-    const uint64_t ms = __ballot(active && decided && st == NW_OK);
-    if (ms && lane == (uint32_t)__builtin_ctzll(ms))
-      atomicAdd(settled + ((q >> 6) & (kCombStatLanes - 1)),
-                (unsigned long long)__builtin_popcountll(ms));
-  }
-  const bool keep = active && st == NW_OK && !decided;
-  const uint64_t m = __ballot(keep);
-  if (m == 0) return;
-  const uint32_t rank = (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull));
-  const uint32_t leader = (uint32_t)__builtin_ctzll(m);
-  uint32_t base = 0;
-  if (lane == leader) base = atomicAdd(count, (uint32_t)__builtin_popcountll(m));
-  base = (uint32_t)__shfl((int)base, (int)leader);
-  if (!keep) return;
-  const uint64_t pos = (uint64_t)base + rank;
-  list[pos] = (uint32_t)j;
-  if (slot != kNoSlot) {
-    xs[pos] = slot;
-  } else {
-#pragma unroll
-    for (int k = 0; k < 10; ++k) xs[(uint64_t)k * cap + pos] = xa.v[k];
-  }
-#pragma unroll
-  for (int k = 0; k < 10; ++k) xs[(uint64_t)(10 + k) * cap + pos] = xr.v[k];
-  // the survivors' scalar phase, after the x limbs are stored (nothing of the decompression
-  // is live here); the lanes of rejected items have left
-  uint32_t dig[kStrictDigitWords], meta;
-  strict_triage_scalars<NW_BWIN>(src, dig, meta);
-#pragma unroll
-  for (int t = 0; t < kStrictDigitWords; ++t) xs[(uint64_t)(20 + t) * cap + pos] = dig[t];
-  xs[(uint64_t)(20 + kStrictDigitWords) * cap + pos] = meta | (slot != kNoSlot ? kMetaSharedA : 0u);
-}
+// (the kernel's text: nw_strict_triage_kernel.hpp, once per source of an item's inputs)
+#define NW_TRIAGE_KERNEL k_strict_triage
+#define NW_TRIAGE_SRC strict_src_global
+#include "nw_strict_triage_kernel.hpp"
+// The triage of a launch over messages of any length: k comes from the k plane (msgs, stride 8).
+#define NW_TRIAGE_KERNEL k_strict_triage_k
+#define NW_TRIAGE_SRC strict_src_plane
+#include "nw_strict_triage_kernel.hpp"
 
 // ---- the slice's key set (nw_strict.hpp keyset_probe / keyset_build) ----
 struct keyset_atomics {
@@ -625,6 +623,7 @@ __global__ __launch_bounds__(256, NW_STRICT_WAVES) void k_verify_strict_pre(
 // status 0 for a pass, X' / Z' in the planes for a pending parity, the state word: kVoteFail
 // for an item without a key or one that left the check before the comb sum, kVoteDecided for
 // one whose sum ran and gave Y' != y_R Z' (nw_strict.hpp keyed_vote_check_ex).
+template <class Src = strict_src_global>
 __device__ __forceinline__ void strict_keyed_item(
     const uint32_t* __restrict__ msgs, uint32_t msg_stride_words, const uint32_t* __restrict__ pks,
     const uint32_t* __restrict__ sigs, uint64_t gi, uint64_t i, int32_t* __restrict__ status,
@@ -632,8 +631,7 @@ __device__ __forceinline__ void strict_keyed_item(
     const ge_niels_pad* __restrict__ bcomb, const vote_planes_t& vp) {
   uint32_t st = kVoteFail;
   if (tab) {
-    const strict_src_global src{pks + 8 * gi, sigs + 16 * gi,
-                                msgs + (uint64_t)msg_stride_words * gi};
+    const Src src{pks + 8 * gi, sigs + 16 * gi, msgs + (uint64_t)msg_stride_words * gi};
     fe X, Z;
     st = keyed_vote_check_ex(src, g_consts.sk, bcomb_wide{bcomb}, keytab_wide{tab, ks}, *okword, X,
                              Z);
@@ -648,11 +646,13 @@ __device__ __forceinline__ void strict_keyed_item(
   if (st == kVotePass) status[gi] = NW_OK;
   vp.state[i] = st;
 }
-template <bool HOT>
-__global__ __launch_bounds__(256, HOT ? NW_COMB_WAVES : NW_KEYED_WAVES) void k_strict_keyed(
+// (k_strict_keyed's body over either source of an item's inputs: inlined into k_strict_keyed
+// it compiles to the instructions the kernel had with the body written in it)
+template <bool HOT, class Src>
+__device__ __forceinline__ void strict_keyed_body(
     const uint32_t* __restrict__ msgs, uint32_t msg_stride_words, const uint32_t* __restrict__ pks,
     const uint32_t* __restrict__ sigs, uint64_t i0, uint64_t ns, int32_t* __restrict__ status,
-    key_tables_t keys, const ge_niels_pad* __restrict__ bcomb, vote_planes_t vp,
+    const key_tables_t& keys, const ge_niels_pad* __restrict__ bcomb, const vote_planes_t& vp,
     uint64_t vk0, const uint32_t* __restrict__ slotmap, const uint32_t* __restrict__ nlive,
     unsigned long long* __restrict__ checked) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -670,19 +670,40 @@ __global__ __launch_bounds__(256, HOT ? NW_COMB_WAVES : NW_KEYED_WAVES) void k_s
       atomicAdd(checked, (unsigned long long)__builtin_popcountll(m));
   }
   const bool has = kk != kNoKey;
-  strict_keyed_item(msgs, msg_stride_words, pks, sigs, gi, i, status,
-                    has ? keys.tabs + keys.ks.tab * (uint64_t)kk : nullptr, keys.ks,
-                    keys.ok + (has ? kk : 0u), bcomb, vp);
+  strict_keyed_item<Src>(msgs, msg_stride_words, pks, sigs, gi, i, status,
+                         has ? keys.tabs + keys.ks.tab * (uint64_t)kk : nullptr, keys.ks,
+                         keys.ok + (has ? kk : 0u), bcomb, vp);
+}
+template <bool HOT>
+__global__ __launch_bounds__(256, HOT ? NW_COMB_WAVES : NW_KEYED_WAVES) void k_strict_keyed(
+    const uint32_t* __restrict__ msgs, uint32_t msg_stride_words, const uint32_t* __restrict__ pks,
+    const uint32_t* __restrict__ sigs, uint64_t i0, uint64_t ns, int32_t* __restrict__ status,
+    key_tables_t keys, const ge_niels_pad* __restrict__ bcomb, vote_planes_t vp,
+    uint64_t vk0, const uint32_t* __restrict__ slotmap, const uint32_t* __restrict__ nlive,
+    unsigned long long* __restrict__ checked) {
+  strict_keyed_body<HOT, strict_src_global>(msgs, msg_stride_words, pks, sigs, i0, ns, status,
+                                            keys, bcomb, vp, vk0, slotmap, nlive, checked);
+}
+// k_strict_keyed<true> of a launch over messages of any length: k from the k plane (msgs).
+__global__ __launch_bounds__(256, NW_COMB_WAVES) void k_strict_keyed_hot_k(
+    const uint32_t* __restrict__ msgs, uint32_t msg_stride_words, const uint32_t* __restrict__ pks,
+    const uint32_t* __restrict__ sigs, uint64_t i0, uint64_t ns, int32_t* __restrict__ status,
+    key_tables_t keys, const ge_niels_pad* __restrict__ bcomb, vote_planes_t vp,
+    uint64_t vk0, const uint32_t* __restrict__ slotmap, const uint32_t* __restrict__ nlive,
+    unsigned long long* __restrict__ checked) {
+  strict_keyed_body<true, strict_src_plane>(msgs, msg_stride_words, pks, sigs, i0, ns, status,
+                                            keys, bcomb, vp, vk0, slotmap, nlive, checked);
 }
 // The HOT instance over one index space (k_strict_comb_select with registered signers): index
 // kk < nreg is row kk of the registry's tables (rtabs, rok), any other one call-local table
 // kk - nreg of `keys`, valid below *nhot. A kernel of its own, so that k_strict_keyed<true>
 // keeps its code object; it counts nothing (k_strict_signers_count does, afterwards).
 // *nlive == 0: no hot key and no registered key in the slice, the triage takes all of it.
-__global__ __launch_bounds__(256, NW_COMB_WAVES) void k_strict_keyed_signers(
+template <class Src>
+__device__ __forceinline__ void strict_keyed_signers_body(
     const uint32_t* __restrict__ msgs, uint32_t msg_stride_words, const uint32_t* __restrict__ pks,
     const uint32_t* __restrict__ sigs, uint64_t i0, uint64_t ns, int32_t* __restrict__ status,
-    key_tables_t keys, const ge_niels_pad* __restrict__ bcomb, vote_planes_t vp,
+    const key_tables_t& keys, const ge_niels_pad* __restrict__ bcomb, const vote_planes_t& vp,
     const uint32_t* __restrict__ slotmap, const uint32_t* __restrict__ nhot,
     const uint32_t* __restrict__ nlive, const ge_niels_pad* __restrict__ rtabs,
     const uint32_t* __restrict__ rok, uint32_t nreg) {
@@ -696,9 +717,32 @@ __global__ __launch_bounds__(256, NW_COMB_WAVES) void k_strict_keyed_signers(
     if (kk >= *nhot) kk = kNoKey;
   }
   const bool has = kk != kNoKey;
-  strict_keyed_item(msgs, msg_stride_words, pks, sigs, i0 + i, i, status,
-                    has ? (reg ? rtabs : keys.tabs) + keys.ks.tab * (uint64_t)kk : nullptr, keys.ks,
-                    (reg ? rok : keys.ok) + (has ? kk : 0u), bcomb, vp);
+  strict_keyed_item<Src>(msgs, msg_stride_words, pks, sigs, i0 + i, i, status,
+                         has ? (reg ? rtabs : keys.tabs) + keys.ks.tab * (uint64_t)kk : nullptr,
+                         keys.ks, (reg ? rok : keys.ok) + (has ? kk : 0u), bcomb, vp);
+}
+__global__ __launch_bounds__(256, NW_COMB_WAVES) void k_strict_keyed_signers(
+    const uint32_t* __restrict__ msgs, uint32_t msg_stride_words, const uint32_t* __restrict__ pks,
+    const uint32_t* __restrict__ sigs, uint64_t i0, uint64_t ns, int32_t* __restrict__ status,
+    key_tables_t keys, const ge_niels_pad* __restrict__ bcomb, vote_planes_t vp,
+    const uint32_t* __restrict__ slotmap, const uint32_t* __restrict__ nhot,
+    const uint32_t* __restrict__ nlive, const ge_niels_pad* __restrict__ rtabs,
+    const uint32_t* __restrict__ rok, uint32_t nreg) {
+  strict_keyed_signers_body<strict_src_global>(msgs, msg_stride_words, pks, sigs, i0, ns, status,
+                                               keys, bcomb, vp, slotmap, nhot, nlive, rtabs, rok,
+                                               nreg);
+}
+// The same of a launch over messages of any length: k from the k plane (msgs).
+__global__ __launch_bounds__(256, NW_COMB_WAVES) void k_strict_keyed_signers_k(
+    const uint32_t* __restrict__ msgs, uint32_t msg_stride_words, const uint32_t* __restrict__ pks,
+    const uint32_t* __restrict__ sigs, uint64_t i0, uint64_t ns, int32_t* __restrict__ status,
+    key_tables_t keys, const ge_niels_pad* __restrict__ bcomb, vote_planes_t vp,
+    const uint32_t* __restrict__ slotmap, const uint32_t* __restrict__ nhot,
+    const uint32_t* __restrict__ nlive, const ge_niels_pad* __restrict__ rtabs,
+    const uint32_t* __restrict__ rok, uint32_t nreg) {
+  strict_keyed_signers_body<strict_src_plane>(msgs, msg_stride_words, pks, sigs, i0, ns, status,
+                                              keys, bcomb, vp, slotmap, nhot, nlive, rtabs, rok,
+                                              nreg);
 }
 
 // Parity of the pending items (Montgomery's trick per strided chunk, as k_votes_keyed_inv).
@@ -1483,8 +1527,8 @@ size_t strict_workspace_bytes() { return strict_tabs_bytes() + strict_keyed_regi
 constexpr uint64_t kTriageSlice = 1ull << 24;
 static_assert(kTriageSlice <= (uint64_t)kTodoDecided,
               "a to-do entry holds the slice item below bit 31 (comb_todo_entry)");
-uint64_t strict_triage_slice(uint64_t n) {
-  if (!strict_triage_on()) return 0;
+uint64_t strict_triage_slice(uint64_t n, bool always) {
+  if (!always && !strict_triage_on()) return 0;
   uint64_t lim = kTriageSlice;
   if (const char* e = getenv("NW_TRIAGE_SLICE")) {
     const unsigned long long v = strtoull(e, nullptr, 10);
@@ -1516,9 +1560,9 @@ size_t strict_comb_bytes(uint64_t slice, uint64_t key_slots, uint64_t hot_cap) {
   return comb_plan(slice, key_slots, hot_cap).bytes;
 }
 
-strict_launch_plan_t strict_launch_plan(uint64_t n, uint32_t registered) {
+strict_launch_plan_t strict_launch_plan(uint64_t n, uint32_t registered, bool always) {
   strict_launch_plan_t p;
-  if (n == 0 || (p.slice = strict_triage_slice(n)) == 0) return p;
+  if (n == 0 || (p.slice = strict_triage_slice(n, always)) == 0) return p;
   p.key_slots = strict_keys_slots(p.slice);
   // NW_STRICT_COMB_DECIDE=0: the comb path's to-do entries carry no verdict, so every listed
   // item that survives the triage takes the ladder (rounds 9-10's sequence; A/B hook)
@@ -1698,6 +1742,9 @@ struct strict_items_t {   // what a launch verifies, and where its verdicts go
   int32_t* status;
   uint64_t* bitmap;
   hipStream_t stream;
+  // msgs is the k plane (launch_verify_strict_msgs: stride 8 words, k of item i at msgs + 8 i):
+  // the two-pass launch runs its plane-reading instances of the kernels that evaluate k
+  bool kplane = false;
 };
 // k_strict_todo_list and k_strict_signers_count: a block takes kTodoPer x 256 consecutive items
 unsigned todo_grid(uint64_t ns) { return grid_for(ns, 256 * kTodoPer); }
@@ -1773,13 +1820,14 @@ hipError_t strict_two_pass_slice(const strict_items_t& in, const strict_ws_t& ws
     const vote_planes_t vp{tv.planes, tv.planes + 20 * slice, slice, nullptr};
     const key_tables_t hk{cv.tabs, cv.hok, tv.keyslot, ks8};
     if (reg_on)
-      hipLaunchKernelGGL(k_strict_keyed_signers, per_item, lanes, 0, stream, in.msgs,
-                         in.msg_stride_words, in.pks, in.sigs, i0, ns, in.status, hk, bcomb, vp,
-                         cv.hotidx, &cb->nhot, &cb->nlive, sg.tabs, sg.ok, sg.n);
+      hipLaunchKernelGGL(in.kplane ? k_strict_keyed_signers_k : k_strict_keyed_signers, per_item,
+                         lanes, 0, stream, in.msgs, in.msg_stride_words, in.pks, in.sigs, i0, ns,
+                         in.status, hk, bcomb, vp, cv.hotidx, &cb->nhot, &cb->nlive, sg.tabs, sg.ok,
+                         sg.n);
     else
-      hipLaunchKernelGGL(k_strict_keyed<true>, per_item, lanes, 0, stream, in.msgs,
-                         in.msg_stride_words, in.pks, in.sigs, i0, ns, in.status, hk, bcomb, vp, 0,
-                         cv.hotidx, &cb->nhot, &cb->checked);
+      hipLaunchKernelGGL(in.kplane ? k_strict_keyed_hot_k : k_strict_keyed<true>, per_item, lanes,
+                         0, stream, in.msgs, in.msg_stride_words, in.pks, in.sigs, i0, ns,
+                         in.status, hk, bcomb, vp, 0, cv.hotidx, &cb->nhot, &cb->checked);
     const uint64_t nchunks = inv_chunks(ns);
     hipLaunchKernelGGL(k_strict_keyed_inv, dim3(grid_for(nchunks, 256)), lanes, 0, stream, i0, ns,
                        nchunks, in.status, vp, live);
@@ -1790,9 +1838,11 @@ hipError_t strict_two_pass_slice(const strict_items_t& in, const strict_ws_t& ws
     hipLaunchKernelGGL(k_strict_todo_list, dim3(todo_grid(ns)), lanes, 0, stream, ns, vp.state,
                        cv.todo, todo_count, live, (uint32_t)ws.plan.comb_decide);
   }
-  hipLaunchKernelGGL(k_strict_triage, per_item, lanes, 0, stream, in.msgs, in.msg_stride_words,
-                     in.pks, in.sigs, i0, ns, in.status, tv.planes, slice, tv.list, &tb->count,
-                     tv.keyslot, tv.kflags, cv.todo, todo_count, listed, live, settled);
+  hipLaunchKernelGGL(in.kplane ? k_strict_triage_k : k_strict_triage, per_item, lanes, 0, stream,
+                     in.msgs, in.msg_stride_words, in.pks, in.sigs, i0, ns, in.status, tv.planes,
+                     slice, tv.list, &tb->count, tv.keyslot, tv.kflags, cv.todo, todo_count, listed,
+                     live, settled);
+  // (the ladder reads the scalar words the triage stored, never k: one instance serves both)
   hipLaunchKernelGGL(k_verify_strict_pre, dim3(std::min<uint64_t>(strict_grid(), per_item.x)),
                      lanes, 0, stream, in.msgs, in.msg_stride_words, in.pks, in.sigs, i0, tv.list,
                      &tb->count, tv.planes, slice, in.status, static_cast<ge_cached_pk*>(ws.base),
@@ -1910,6 +1960,27 @@ hipError_t launch_verify_strict(const uint32_t* msgs, uint32_t msg_stride_words,
                               : launch_strict_one_pass(in, ws.base, kt, btw, nullptr);
   return env_is_zero("NW_STRICT_KEYED_FAST") ? launch_strict_one_pass(in, ws.base, kt, btw, bcomb)
                                              : launch_strict_keyed_fast(in, ws.base, kt, btw, bcomb);
+}
+
+// The strict launch over messages of any length: k of every item into the plane, then the
+// two-pass launch (always: NW_STRICT_TRIAGE=0 is an A/B hook of the 32-byte launch) with the
+// plane in the place of the digests.
+hipError_t launch_verify_strict_msgs(const uint8_t* data, const uint64_t* offsets,
+                                     const uint64_t* lengths, const uint32_t* pks,
+                                     const uint32_t* sigs, uint64_t n, int32_t* status,
+                                     uint64_t* bitmap, const strict_ws_t& ws, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  if (!ws.kplane) return hipErrorInvalidValue;
+  const ge_niels_pad* btw = nullptr;
+  hipError_t e = btab_for_current_device(0, &btw);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_strict_hram, dim3(grid_for(n, 256)), dim3(256), 0, stream, data, offsets,
+                     lengths, pks, sigs, n, ws.kplane);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  strict_items_t in{ws.kplane, 8, pks, sigs, n, status, bitmap, stream};
+  in.kplane = true;
+  return launch_strict_two_pass(in, ws, btw);
 }
 
 size_t votes_keyed_bytes_per_vote() { return 4 * 22; }   // 20 limb planes, state, perm

@@ -105,7 +105,11 @@ class Lease {
   // unkeyed launch of n items (n = 0: keyed, none), that launch's plan (nw::strict_launch_plan)
   // and the regions it needs: the two-pass path's slice (nw::strict_triage_bytes(plan.slice,
   // plan.key_slots)) and, with the comb path, its tables (nw::strict_comb_bytes); grow-only.
-  int strict_ws(nw::strict_ws_t* out, size_t n);
+  // msgs: the launch is nw::launch_verify_strict_msgs, which always runs two passes and also
+  // needs the device's k plane (32 bytes per item of the call: an allocation of its own,
+  // grow-only, in out->kplane). NW_E_OUT_OF_MEMORY when the plane cannot be had; the device's
+  // other buffers stay as they are.
+  int strict_ws(nw::strict_ws_t* out, size_t n, bool msgs = false);
   // Key tables for nkeys keys (grow-only at one comb width, nw_api.cpp key_width): tabs
   // (nw::key_tables_bytes) and ok words, their layout (ks), plus the reuse state of
   // nw::launch_key_tables: the device copy of the keys they were last built from, the
