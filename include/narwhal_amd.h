@@ -256,6 +256,14 @@ int nw_dev_strict_comb_stats(uint64_t out[4], void* stream);
  * nw_dev_strict_comb_stats. Waits for `stream` first. Both zero before the first launch and when
  * the comb path is off. Tests and tools only. */
 int nw_dev_strict_decided_stats(uint64_t out[2], void* stream);
+/* Key-major order of the same launch's comb check: a slice of many items under many hot keys is
+ * sorted by key on the device before the check, so that the lanes running at one time read a few
+ * keys' tables (NW_STRICT_KEY_MAJOR, read per launch: 0 = item order, 1 = every slice is sorted,
+ * unset = slices of at least 2^20 items with at least 64 live keys; no status depends on it).
+ * out[0] = items with a live key that the sort placed, out[1] = key bins that held an item,
+ * out[2] = slices sorted, each summed over the slices; all zero for a launch in item order and
+ * before the first launch. Waits for `stream` first. Tests and tools only. */
+int nw_dev_strict_keymajor_stats(uint64_t out[3], void* stream);
 /* Registered signers: keys that sign most of what a caller sends (a network's primaries, workers
  * and clients) keep their 8-bit comb tables (528 KB per key) on the device across calls, so
  * their items take the comb check in every unkeyed strict launch, whatever its size

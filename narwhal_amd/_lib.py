@@ -65,6 +65,7 @@ def prototypes() -> dict:
         "nw_dev_strict_keyset_stats": ([P, P], I),
         "nw_dev_strict_comb_stats": ([P, P], I),
         "nw_dev_strict_decided_stats": ([P, P], I),
+        "nw_dev_strict_keymajor_stats": ([P, P], I),
         "nw_strict_signers_set": ([P, S], I),
         "nw_strict_signers_count": ([P], I),
         "nw_dev_strict_signers_stats": ([P, P], I),

@@ -48,6 +48,8 @@ struct SharedDev {
   uint64_t triage_keys = 0;    // key-set slots the region holds (nw::strict_keys_slots)
   void* comb_ws = nullptr;     // the hot keys' comb tables (grow-only, nw::strict_comb_bytes)
   uint64_t comb_slice = 0, comb_slots = 0, comb_keys = 0;   // what it was sized for
+  void* km_ws = nullptr;       // key-major order of a slice (grow-only, nw::strict_keymajor_bytes)
+  uint64_t km_slice = 0;       // items it was sized for
   void* kplane = nullptr;      // k of every item of a launch over messages of any length
   uint64_t kplane_cap = 0;     // items (32 bytes each; grow-only)
   nw::strict_signers_t signers;   // the registered signers: an allocation of their own, which
@@ -337,6 +339,15 @@ int nw_dev_strict_comb_stats(uint64_t out[4], void* stream) {
   if (rc) return rc;
   if (!out) return set_err(NW_E_INVALID_ARG, "null pointer");
   NW_HIP(nw::strict_comb_stats(out, pick_stream(stream, c)), "strict comb statistics");
+  return 0;
+}
+
+int nw_dev_strict_keymajor_stats(uint64_t out[3], void* stream) {
+  DevCtx* c;
+  int rc = begin(&c);
+  if (rc) return rc;
+  if (!out) return set_err(NW_E_INVALID_ARG, "null pointer");
+  NW_HIP(nw::strict_keymajor_stats(out, pick_stream(stream, c)), "strict key-major statistics");
   return 0;
 }
 
@@ -1302,8 +1313,25 @@ int Lease::strict_ws(nw::strict_ws_t* out, size_t n, bool msgs) {
     p.hot_cap = 0;
     p.signers = false;
   }
+  // the key-major order's region: an allocation of its own, grown with the slice; when it cannot
+  // be had the launch runs in item order
+  if (!p.comb()) p.key_major = false;
+  if (p.key_major && d.triage_cap > d.km_slice) {
+    if (d.km_ws) {
+      if (d.last_valid) (void)hipEventSynchronize(d.last);
+      (void)hipFree(d.km_ws);
+    }
+    d.km_ws = nullptr;
+    d.km_slice = 0;
+    if (nw::table_malloc(&d.km_ws, nw::strict_keymajor_bytes(d.triage_cap)) == hipSuccess)
+      d.km_slice = d.triage_cap;
+    else
+      d.km_ws = nullptr;
+  }
+  if (!d.km_ws) p.key_major = false;
   *out = nw::strict_ws_t{d.strict_ws, d.triage_ws, p.comb() ? d.comb_ws : nullptr,
-                         {d.triage_cap, d.triage_keys, d.comb_keys}, p,
+                         p.key_major ? d.km_ws : nullptr,
+                         {d.triage_cap, d.triage_keys, d.comb_keys, d.km_slice}, p,
                          p.signers ? d.signers : nw::strict_signers_t{},
                          msgs ? static_cast<uint32_t*>(d.kplane) : nullptr};
   return 0;

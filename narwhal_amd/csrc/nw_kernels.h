@@ -6,6 +6,7 @@
 
 #include "narwhal_amd.h"
 #include "nw_strict_layout.hpp"
+#include "nw_strict_keymajor.hpp"
 
 namespace nw {
 
@@ -95,7 +96,8 @@ uint64_t strict_signers_min_items();
 // them. Synchronises `stream`.
 hipError_t strict_signers_stats(uint64_t out[3], hipStream_t stream);
 // One launch's plan (the knobs, read once per launch: NW_TRIAGE_SLICE, NW_STRICT_KEYS,
-// NW_STRICT_COMB / _MIN / _KEYS, NW_STRICT_SIGNERS_MIN_ITEMS, NW_STRICT_COMB_DECIDE) for n items
+// NW_STRICT_COMB / _MIN / _KEYS, NW_STRICT_SIGNERS_MIN_ITEMS, NW_STRICT_COMB_DECIDE,
+// NW_STRICT_KEY_MAJOR) for n items
 // on a device with `registered` registered signers. n = 0 (a keyed launch), or the two-pass
 // path off: the empty plan.
 struct strict_launch_plan_t {
@@ -107,18 +109,37 @@ struct strict_launch_plan_t {
   bool comb_decide = true;   // the to-do entries carry the comb's verdict
   // the comb path runs: with registered signers even without room for a call-local table
   bool comb() const { return hot_cap != 0 || signers; }
+  // Key-major order of the comb path's lanes (nw_strict_keymajor.hpp; NW_STRICT_KEY_MAJOR, read
+  // per launch: 0 = item order, the kernel sequence without the sort; 1 = every slice is sorted;
+  // unset = the host's part of the decision here, slice >= kKmAutoSlice, and the device's in
+  // the kernels, live keys of the slice >= km_min_live).
+  bool key_major = false;
+  uint32_t km_min_live = 0;
 };
+// The automatic decision's thresholds (DESIGN.md 5 "Round 16" has the rows behind them): the
+// smallest slice and the fewest live keys at which the sorted launch measured faster (2^20
+// items under 4,096 keys: 8.52 -> 7.75 ms; 12.5M under 64: 25.4 -> 23.6 ms); 65,536 items
+// measured no gain under 4,096 keys and 2 % slower under 64, fewer than 64 keys were not measured.
+constexpr uint64_t kKmAutoSlice = 1ull << 20;
+constexpr uint32_t kKmAutoLive = 64;
+size_t strict_keymajor_bytes(uint64_t slice);
+// For the last unkeyed two-pass launch queued on the current device: items with a live key that
+// the sort placed, key bins that held an item, slices sorted (each summed over the slices); all 0
+// for a launch in item order. Synchronises `stream`.
+hipError_t strict_keymajor_stats(uint64_t out[3], hipStream_t stream);
 // always: plan the two-pass launch whatever NW_STRICT_TRIAGE says (launch_verify_strict_msgs).
 strict_launch_plan_t strict_launch_plan(uint64_t n, uint32_t registered, bool always = false);
 // What Lease::strict_ws hands a launch: the allocations, what they hold and the launch's plan.
 struct strict_caps_t {
   uint64_t slice = 0, key_slots = 0;   // triage: strict_triage_bytes(slice, key_slots)
   uint64_t hot_keys = 0;               // comb: strict_comb_bytes(slice, key_slots, hot_keys)
+  uint64_t km_slice = 0;               // key-major order: strict_keymajor_bytes(km_slice)
 };
 struct strict_ws_t {
   void* base = nullptr;       // strict_workspace_bytes()
   void* triage = nullptr;     // null for a keyed launch
   void* comb = nullptr;       // null: the launch runs without the comb path
+  void* keymajor = nullptr;   // null: the launch runs in item order
   strict_caps_t caps;
   strict_launch_plan_t plan;  // without comb: hot_cap = 0 and signers = false
   strict_signers_t signers;   // the device's registered signers when plan.signers (else n == 0)

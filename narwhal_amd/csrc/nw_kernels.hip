@@ -550,6 +550,115 @@ __global__ __launch_bounds__(256) void k_strict_comb_select(
   hotidx[s] = h;
 }
 
+// Key-major order of the slice (nw_strict_keymajor.hpp): a counting sort of its items by the
+// index the comb kernels use, hotidx[keyslot[i]], in groups of 2^shift indices; every item
+// without a live key goes to the last bin. k_km_hist / k_km_scan / k_km_scatter follow the
+// votes' k_vk_* below: blocks take contiguous chunks of kKmChunk items, count them in an LDS
+// histogram and touch global memory with ONE atomic per (block, bin used) and pass; positions
+// inside a block's range of a bin come from LDS cursors. 12.5M items under 4,096 keys: 763
+// blocks x ~513 bins, 0.39M atomics per pass over 513 addresses (a block per 256 items, or a
+// bin per key, would be millions on as many addresses as the votes' 4.9 ms pass had).
+// The counts are exact and the sort's own (uses[] is a sampled estimate). All three exit when
+// the slice has fewer than min_live live keys, a word every kernel of the slice reads alike.
+struct km_keys_t {
+  const uint32_t* keyslot;   // item -> slot of the slice's key set, or kNoSlot
+  const uint32_t* hotidx;    // slot -> key index, or kNoKey (k_strict_comb_select)
+  const uint32_t* nhot;      // call-local tables taken; may end above hot_cap
+  const uint32_t* live;      // the slice's live keys (comb_block_t nhot or nlive)
+  uint32_t nreg, hot_cap, min_live;
+};
+__device__ __forceinline__ uint32_t km_space(const km_keys_t& k) {
+  const uint32_t nhot = *k.nhot;
+  return k.nreg + (nhot < k.hot_cap ? nhot : k.hot_cap);
+}
+__device__ __forceinline__ uint32_t km_item_bin(const km_keys_t& k, uint64_t i, uint32_t space,
+                                                uint32_t shift, uint32_t* slot_out) {
+  const uint32_t slot = k.keyslot[i];
+  *slot_out = slot;
+  return km_bin(slot != kNoSlot ? k.hotidx[slot] : kNoKey, space, shift);
+}
+__global__ __launch_bounds__(256) void k_km_hist(uint64_t ns, km_keys_t k,
+                                                 uint32_t* __restrict__ gh) {
+  __shared__ uint32_t h[kKmBins];
+  if (*k.live < k.min_live) return;
+  const uint32_t space = km_space(k), shift = km_shift(space);
+  for (uint32_t b = threadIdx.x; b < kKmBins; b += blockDim.x) h[b] = 0;
+  __syncthreads();
+  const uint64_t c0 = (uint64_t)blockIdx.x * kKmChunk;
+  const uint64_t c1 = c0 + kKmChunk < ns ? c0 + kKmChunk : ns;
+  uint32_t slot;
+  for (uint64_t i = c0 + threadIdx.x; i < c1; i += blockDim.x)
+    atomicAdd(&h[km_item_bin(k, i, space, shift, &slot)], 1u);
+  __syncthreads();
+  for (uint32_t b = threadIdx.x; b < kKmBins; b += blockDim.x)
+    if (h[b]) atomicAdd(&gh[b], h[b]);
+}
+// One block of kKmBins lanes: cursor[b] = the first position of bin b (an exclusive scan of
+// the histogram, which is left zero for the next slice), *npos = the last bin's, the
+// launch's counters.
+__global__ __launch_bounds__(kKmBins) void k_km_scan(uint32_t* __restrict__ gh,
+                                                     uint32_t* __restrict__ cursor,
+                                                     km_block_t* __restrict__ blk,
+                                                     const uint32_t* __restrict__ live,
+                                                     uint32_t min_live) {
+  __shared__ uint32_t s[kKmBins];
+  __shared__ uint32_t s_used[kKmBins / 64];
+  if (*live < min_live) return;
+  const uint32_t b = threadIdx.x;
+  const uint32_t c = gh[b];
+  gh[b] = 0;
+  s[b] = c;
+  const uint64_t used = __ballot(c != 0 && b != kKmBins - 1);
+  if ((b & 63u) == 0) s_used[b >> 6] = (uint32_t)__builtin_popcountll(used);
+  __syncthreads();
+  for (uint32_t d = 1; d < kKmBins; d <<= 1) {   // Hillis-Steele, inclusive
+    const uint32_t v = b >= d ? s[b - d] : 0u;
+    __syncthreads();
+    s[b] += v;
+    __syncthreads();
+  }
+  cursor[b] = s[b] - c;
+  if (b == kKmBins - 1) {
+    const uint32_t npos = s[b] - c;
+    uint32_t bins = 0;
+    for (uint32_t w = 0; w < kKmBins / 64; ++w) bins += s_used[w];
+    blk->npos = npos;
+    blk->placed += npos;   // one lane of one block per slice: no atomic needed
+    blk->bins += bins;
+    blk->slices += 1;
+  }
+}
+// Same chunks: count again, reserve the block's range in every bin it uses (one atomic each),
+// then hand out positions inside the ranges with LDS cursors. perm[p] = the item at position
+// p, pslot[p] = its slot. The positions of all bins together are exactly 0 .. ns - 1.
+__global__ __launch_bounds__(256) void k_km_scatter(uint64_t ns, km_keys_t k,
+                                                    uint32_t* __restrict__ cursor,
+                                                    uint32_t* __restrict__ perm,
+                                                    uint32_t* __restrict__ pslot) {
+  __shared__ uint32_t h[kKmBins];
+  if (*k.live < k.min_live) return;
+  const uint32_t space = km_space(k), shift = km_shift(space);
+  for (uint32_t b = threadIdx.x; b < kKmBins; b += blockDim.x) h[b] = 0;
+  __syncthreads();
+  const uint64_t c0 = (uint64_t)blockIdx.x * kKmChunk;
+  const uint64_t c1 = c0 + kKmChunk < ns ? c0 + kKmChunk : ns;
+  uint32_t slot;
+  for (uint64_t i = c0 + threadIdx.x; i < c1; i += blockDim.x)
+    atomicAdd(&h[km_item_bin(k, i, space, shift, &slot)], 1u);
+  __syncthreads();
+  for (uint32_t x = threadIdx.x; x < kKmBins; x += blockDim.x)
+    if (h[x]) h[x] = atomicAdd(&cursor[x], h[x]);   // this block's range in bin x
+  __syncthreads();
+  for (uint64_t i = c0 + threadIdx.x; i < c1; i += blockDim.x) {
+    const uint32_t b = km_item_bin(k, i, space, shift, &slot);
+    const uint32_t p = atomicAdd(&h[b], 1u);
+    if (p < ns) {   // always: the ranges partition 0 .. ns - 1 (a guard, not a path)
+      perm[p] = (uint32_t)i;
+      pslot[p] = slot;
+    }
+  }
+}
+
 // The list's items (persistent, as k_verify_strict): strict_verify_core on the points
 // k_strict_triage decompressed; *count is read on the device.
 __global__ __launch_bounds__(256, NW_STRICT_WAVES) void k_verify_strict_pre(
@@ -618,20 +727,42 @@ __global__ __launch_bounds__(256, NW_STRICT_WAVES) void k_verify_strict_pre(
 #ifndef NW_COMB_WAVES
 #define NW_COMB_WAVES 1
 #endif
+// Key-major order of the HOT instances' lanes (nw_strict_keymajor.hpp; the order itself is
+// vote_planes_t's perm, null for a launch in item order): what a lane needs besides it.
+struct km_order_t {
+  const uint32_t* pslot;   // position -> the item's slot in the slice's key set
+  const uint32_t* slots;   // the key set: slot -> its owner's row in the slice + 1
+  uint32_t min_live;       // the slice is sorted when it has at least this many live keys
+};
+// The device's part of the decision, taken alike by the sort kernels and by every kernel that
+// reads the order, from words that are final once k_strict_comb_select has run.
+__device__ __forceinline__ bool km_sorted(const uint32_t* perm, uint32_t live, uint32_t min_live) {
+  return perm != nullptr && live >= min_live;
+}
+__device__ __forceinline__ bool km_sorted(const uint32_t* perm, uint32_t live,
+                                          const km_order_t& km) {
+  return km_sorted(perm, live, km.min_live);
+}
+__device__ __forceinline__ const km_order_t* km_ptr() { return nullptr; }
+__device__ __forceinline__ const km_order_t* km_ptr(const km_order_t& km) { return &km; }
+
 // The check of slice item i (global item gi) under the key whose comb tables are `tab` and whose
 // flag word is *okword (tab == nullptr: the item has no key here) and what it leaves behind:
 // status 0 for a pass, X' / Z' in the planes for a pending parity, the state word: kVoteFail
 // for an item without a key or one that left the check before the comb sum, kVoteDecided for
 // one whose sum ran and gave Y' != y_R Z' (nw_strict.hpp keyed_vote_check_ex).
+// i is the item's place in the planes (its slice index, or its position in key-major order);
+// key_row the row of pks that holds its key's 32 bytes (gi, or the row of any item of the same
+// slot of the key set, which compares all 32 bytes).
 template <class Src = strict_src_global>
 __device__ __forceinline__ void strict_keyed_item(
     const uint32_t* __restrict__ msgs, uint32_t msg_stride_words, const uint32_t* __restrict__ pks,
     const uint32_t* __restrict__ sigs, uint64_t gi, uint64_t i, int32_t* __restrict__ status,
     const ge_niels_pad* __restrict__ tab, const keyspec& ks, const uint32_t* __restrict__ okword,
-    const ge_niels_pad* __restrict__ bcomb, const vote_planes_t& vp) {
+    const ge_niels_pad* __restrict__ bcomb, const vote_planes_t& vp, uint64_t key_row) {
   uint32_t st = kVoteFail;
   if (tab) {
-    const Src src{pks + 8 * gi, sigs + 16 * gi, msgs + (uint64_t)msg_stride_words * gi};
+    const Src src{pks + 8 * key_row, sigs + 16 * gi, msgs + (uint64_t)msg_stride_words * gi};
     fe X, Z;
     st = keyed_vote_check_ex(src, g_consts.sk, bcomb_wide{bcomb}, keytab_wide{tab, ks}, *okword, X,
                              Z);
@@ -654,35 +785,50 @@ __device__ __forceinline__ void strict_keyed_body(
     const uint32_t* __restrict__ sigs, uint64_t i0, uint64_t ns, int32_t* __restrict__ status,
     const key_tables_t& keys, const ge_niels_pad* __restrict__ bcomb, const vote_planes_t& vp,
     uint64_t vk0, const uint32_t* __restrict__ slotmap, const uint32_t* __restrict__ nlive,
-    unsigned long long* __restrict__ checked) {
+    unsigned long long* __restrict__ checked, const km_order_t* km) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= ns) return;
   if constexpr (HOT) {
     if (*nlive == 0) return;   // no hot key: the triage takes the whole slice
   }
-  const uint64_t gi = i0 + i;
-  uint32_t kk = keys.vote_key[vk0 + i];
+  uint64_t gi = i0 + i, key_row = gi;
+  uint32_t kk;
   if constexpr (HOT) {
+    // lane i is position i of the key-major order (vp.perm, nw_strict_keymajor.hpp) when the
+    // slice was sorted, else item i
+    if (km_sorted(vp.perm, *nlive, *km)) {
+      gi = i0 + vp.perm[i];
+      kk = km->pslot[i];
+      key_row = kk != kNoSlot ? i0 + (km->slots[kk] - 1) : gi;
+    } else {
+      kk = keys.vote_key[vk0 + i];
+    }
     kk = kk != kNoSlot ? slotmap[kk] : kNoKey;
     if (kk != kNoKey && kk >= *nlive) kk = kNoKey;
     const uint64_t m = __ballot(kk != kNoKey);
     if (m && (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(m))
       atomicAdd(checked, (unsigned long long)__builtin_popcountll(m));
+  } else {
+    kk = keys.vote_key[vk0 + i];
   }
   const bool has = kk != kNoKey;
   strict_keyed_item<Src>(msgs, msg_stride_words, pks, sigs, gi, i, status,
                          has ? keys.tabs + keys.ks.tab * (uint64_t)kk : nullptr, keys.ks,
-                         keys.ok + (has ? kk : 0u), bcomb, vp);
+                         keys.ok + (has ? kk : 0u), bcomb, vp, key_row);
 }
-template <bool HOT>
+// Km: nothing for the committee instance (HOT = false, whose arguments and code are those it
+// had before the key-major order), one km_order_t for the HOT one.
+template <bool HOT, class... Km>
 __global__ __launch_bounds__(256, HOT ? NW_COMB_WAVES : NW_KEYED_WAVES) void k_strict_keyed(
     const uint32_t* __restrict__ msgs, uint32_t msg_stride_words, const uint32_t* __restrict__ pks,
     const uint32_t* __restrict__ sigs, uint64_t i0, uint64_t ns, int32_t* __restrict__ status,
     key_tables_t keys, const ge_niels_pad* __restrict__ bcomb, vote_planes_t vp,
     uint64_t vk0, const uint32_t* __restrict__ slotmap, const uint32_t* __restrict__ nlive,
-    unsigned long long* __restrict__ checked) {
+    unsigned long long* __restrict__ checked, Km... km) {
+  static_assert(sizeof...(Km) == (HOT ? 1 : 0), "the HOT instance takes the order, no other does");
   strict_keyed_body<HOT, strict_src_global>(msgs, msg_stride_words, pks, sigs, i0, ns, status,
-                                            keys, bcomb, vp, vk0, slotmap, nlive, checked);
+                                            keys, bcomb, vp, vk0, slotmap, nlive, checked,
+                                            km_ptr(km...));
 }
 // k_strict_keyed<true> of a launch over messages of any length: k from the k plane (msgs).
 __global__ __launch_bounds__(256, NW_COMB_WAVES) void k_strict_keyed_hot_k(
@@ -690,9 +836,9 @@ __global__ __launch_bounds__(256, NW_COMB_WAVES) void k_strict_keyed_hot_k(
     const uint32_t* __restrict__ sigs, uint64_t i0, uint64_t ns, int32_t* __restrict__ status,
     key_tables_t keys, const ge_niels_pad* __restrict__ bcomb, vote_planes_t vp,
     uint64_t vk0, const uint32_t* __restrict__ slotmap, const uint32_t* __restrict__ nlive,
-    unsigned long long* __restrict__ checked) {
+    unsigned long long* __restrict__ checked, km_order_t km) {
   strict_keyed_body<true, strict_src_plane>(msgs, msg_stride_words, pks, sigs, i0, ns, status,
-                                            keys, bcomb, vp, vk0, slotmap, nlive, checked);
+                                            keys, bcomb, vp, vk0, slotmap, nlive, checked, &km);
 }
 // The HOT instance over one index space (k_strict_comb_select with registered signers): index
 // kk < nreg is row kk of the registry's tables (rtabs, rok), any other one call-local table
@@ -706,10 +852,18 @@ __device__ __forceinline__ void strict_keyed_signers_body(
     const key_tables_t& keys, const ge_niels_pad* __restrict__ bcomb, const vote_planes_t& vp,
     const uint32_t* __restrict__ slotmap, const uint32_t* __restrict__ nhot,
     const uint32_t* __restrict__ nlive, const ge_niels_pad* __restrict__ rtabs,
-    const uint32_t* __restrict__ rok, uint32_t nreg) {
+    const uint32_t* __restrict__ rok, uint32_t nreg, const km_order_t& km) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= ns || *nlive == 0) return;
-  uint32_t kk = keys.vote_key[i];
+  uint64_t gi = i0 + i, key_row = gi;
+  uint32_t kk;
+  if (km_sorted(vp.perm, *nlive, km)) {   // lane i is position i of the key-major order
+    gi = i0 + vp.perm[i];
+    kk = km.pslot[i];
+    key_row = kk != kNoSlot ? i0 + (km.slots[kk] - 1) : gi;
+  } else {
+    kk = keys.vote_key[i];
+  }
   kk = kk != kNoSlot ? slotmap[kk] : kNoKey;
   const bool reg = kk < nreg;
   if (kk != kNoKey && !reg) {
@@ -717,9 +871,9 @@ __device__ __forceinline__ void strict_keyed_signers_body(
     if (kk >= *nhot) kk = kNoKey;
   }
   const bool has = kk != kNoKey;
-  strict_keyed_item<Src>(msgs, msg_stride_words, pks, sigs, i0 + i, i, status,
+  strict_keyed_item<Src>(msgs, msg_stride_words, pks, sigs, gi, i, status,
                          has ? (reg ? rtabs : keys.tabs) + keys.ks.tab * (uint64_t)kk : nullptr,
-                         keys.ks, (reg ? rok : keys.ok) + (has ? kk : 0u), bcomb, vp);
+                         keys.ks, (reg ? rok : keys.ok) + (has ? kk : 0u), bcomb, vp, key_row);
 }
 __global__ __launch_bounds__(256, NW_COMB_WAVES) void k_strict_keyed_signers(
     const uint32_t* __restrict__ msgs, uint32_t msg_stride_words, const uint32_t* __restrict__ pks,
@@ -727,10 +881,10 @@ __global__ __launch_bounds__(256, NW_COMB_WAVES) void k_strict_keyed_signers(
     key_tables_t keys, const ge_niels_pad* __restrict__ bcomb, vote_planes_t vp,
     const uint32_t* __restrict__ slotmap, const uint32_t* __restrict__ nhot,
     const uint32_t* __restrict__ nlive, const ge_niels_pad* __restrict__ rtabs,
-    const uint32_t* __restrict__ rok, uint32_t nreg) {
+    const uint32_t* __restrict__ rok, uint32_t nreg, km_order_t km) {
   strict_keyed_signers_body<strict_src_global>(msgs, msg_stride_words, pks, sigs, i0, ns, status,
                                                keys, bcomb, vp, slotmap, nhot, nlive, rtabs, rok,
-                                               nreg);
+                                               nreg, km);
 }
 // The same of a launch over messages of any length: k from the k plane (msgs).
 __global__ __launch_bounds__(256, NW_COMB_WAVES) void k_strict_keyed_signers_k(
@@ -739,10 +893,10 @@ __global__ __launch_bounds__(256, NW_COMB_WAVES) void k_strict_keyed_signers_k(
     key_tables_t keys, const ge_niels_pad* __restrict__ bcomb, vote_planes_t vp,
     const uint32_t* __restrict__ slotmap, const uint32_t* __restrict__ nhot,
     const uint32_t* __restrict__ nlive, const ge_niels_pad* __restrict__ rtabs,
-    const uint32_t* __restrict__ rok, uint32_t nreg) {
+    const uint32_t* __restrict__ rok, uint32_t nreg, km_order_t km) {
   strict_keyed_signers_body<strict_src_plane>(msgs, msg_stride_words, pks, sigs, i0, ns, status,
                                               keys, bcomb, vp, slotmap, nhot, nlive, rtabs, rok,
-                                              nreg);
+                                              nreg, km);
 }
 
 // Parity of the pending items (Montgomery's trick per strided chunk, as k_votes_keyed_inv).
@@ -793,12 +947,16 @@ __global__ __launch_bounds__(256) void k_strict_keyed_inv(uint64_t i0, uint64_t 
                                                           uint64_t nchunks,
                                                           int32_t* __restrict__ status,
                                                           vote_planes_t vp,
-                                                          const uint32_t* __restrict__ nlive) {
+                                                          const uint32_t* __restrict__ nlive,
+                                                          uint32_t km_min) {
   // nlive (optional): nothing to do when *nlive == 0 (k_strict_keyed<true> wrote no state)
   const uint64_t lane = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (lane >= nchunks || (nlive && *nlive == 0)) return;
+  // the planes and the state are in position space when the slice was sorted: position i holds
+  // item perm[i]
+  const uint32_t* const perm = nlive && km_sorted(vp.perm, *nlive, km_min) ? vp.perm : nullptr;
   keyed_inv_chunk(lane, ns, nchunks, vp, [&](uint64_t i, bool match) {
-    if (match) status[i0 + i] = NW_OK;
+    if (match) status[i0 + (perm ? perm[i] : i)] = NW_OK;
     else vp.state[i] = comb_parity_state(false);
   });
 }
@@ -834,10 +992,14 @@ __global__ __launch_bounds__(256) void k_strict_todo_list(uint64_t ns,
                                                           uint32_t* __restrict__ list,
                                                           uint32_t* __restrict__ count,
                                                           const uint32_t* __restrict__ nlive,
-                                                          uint32_t decide) {
+                                                          uint32_t decide,
+                                                          const uint32_t* __restrict__ perm,
+                                                          uint32_t km_min) {
   __shared__ uint32_t s_wave[4];
   __shared__ uint32_t s_base;
   if (*nlive == 0) return;   // no hot key, no state: the triage takes the whole slice
+  // a sorted slice: the state is per position, the entry names the item there
+  if (!km_sorted(perm, *nlive, km_min)) perm = nullptr;
   const uint64_t b0 = (uint64_t)blockIdx.x * (256 * kTodoPer);
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   // round r: items b0 + 256 r + threadIdx.x; this wave's failed items of all rounds, counted
@@ -864,10 +1026,12 @@ __global__ __launch_bounds__(256) void k_strict_todo_list(uint64_t ns,
 #pragma unroll
   for (uint32_t r = 0; r < kTodoPer; ++r) {
     const uint64_t m = masks[r];
-    if ((m >> lane) & 1ull)
+    if ((m >> lane) & 1ull) {
+      const uint32_t p = (uint32_t)(b0 + 256 * r + threadIdx.x);
       list[pos + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull))] =
-          comb_todo_entry((uint32_t)(b0 + 256 * r + threadIdx.x),
+          comb_todo_entry(perm ? perm[p] : p,
                           ((dmasks[r] >> lane) & 1ull) ? kVoteDecided : kVoteFail, decide != 0);
+    }
     pos += (uint32_t)__builtin_popcountll(m);
   }
 }
@@ -880,9 +1044,12 @@ __global__ __launch_bounds__(256) void k_strict_todo_list(uint64_t ns,
 __global__ __launch_bounds__(256) void k_strict_signers_count(
     uint64_t ns, const uint32_t* __restrict__ keyslot, const uint32_t* __restrict__ slotmap,
     const uint32_t* __restrict__ nhot, const uint32_t* __restrict__ nlive, uint32_t nreg,
-    const uint32_t* __restrict__ state, unsigned long long* __restrict__ ctr) {
+    const uint32_t* __restrict__ state, unsigned long long* __restrict__ ctr,
+    const uint32_t* __restrict__ perm, const uint32_t* __restrict__ pslot, uint32_t km_min) {
   __shared__ uint32_t s_sum[4][3];
   if (*nlive == 0) return;
+  // a sorted slice: the state is per position, and so is the slot of the item there
+  if (km_sorted(perm, *nlive, km_min)) keyslot = pslot;
   const uint64_t b0 = (uint64_t)blockIdx.x * (256 * kTodoPer);
   uint32_t mine[3] = {0, 0, 0};
 #pragma unroll 1
@@ -1577,8 +1744,17 @@ strict_launch_plan_t strict_launch_plan(uint64_t n, uint32_t registered, bool al
   if (const char* e = getenv("NW_STRICT_COMB_KEYS")) keys = strtoull(e, nullptr, 10);
   p.hot_cap = std::min<uint64_t>({keys, p.slice / p.comb_min, 1ull << 20});
   p.signers = registered != 0 && n >= strict_signers_min_items();
+  // key-major order of the comb path's lanes: small slices and slices of few keys have their
+  // tables in the caches already and stay in item order
+  if (p.comb()) {
+    const char* e = getenv("NW_STRICT_KEY_MAJOR");
+    const bool forced = e && e[0] != '\0' && e[0] != '0';
+    p.key_major = forced || (!e && p.slice >= kKmAutoSlice);
+    p.km_min_live = forced ? 1u : kKmAutoLive;
+  }
   return p;
 }
+size_t strict_keymajor_bytes(uint64_t slice) { return km_region_plan(slice).bytes; }
 
 // ---- diagnostics: the counters of the last unkeyed two-pass launch per device ----
 namespace {
@@ -1587,6 +1763,7 @@ struct two_pass_record_t {
   const comb_block_t* comb = nullptr;       // null: the comb path was off
   uint64_t n = 0;
   bool valid = false, keys_on = false;
+  const km_block_t* km = nullptr;           // null: the launch ran in item order
 };
 std::mutex g_two_pass_m;
 two_pass_record_t g_two_pass_last[64];
@@ -1594,6 +1771,7 @@ struct strict_counters_t {
   two_pass_record_t rec;   // !valid: no launch yet, nothing was read
   triage_block_t triage;   // read when rec.keys_on
   comb_block_t comb;       // read when rec.comb
+  km_block_t km;           // read when rec.km
 };
 // Synchronises `stream`, then copies the blocks that the launch counted in.
 hipError_t strict_last_counters(hipStream_t stream, strict_counters_t* s) {
@@ -1610,6 +1788,8 @@ hipError_t strict_last_counters(hipStream_t stream, strict_counters_t* s) {
     e = hipMemcpy(&s->triage, s->rec.triage, sizeof(s->triage), hipMemcpyDeviceToHost);
   if (e == hipSuccess && s->rec.comb)
     e = hipMemcpy(&s->comb, s->rec.comb, sizeof(s->comb), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && s->rec.km)
+    e = hipMemcpy(&s->km, s->rec.km, sizeof(s->km), hipMemcpyDeviceToHost);
   return e;
 }
 template <size_t N>
@@ -1652,6 +1832,16 @@ hipError_t strict_decided_stats(uint64_t out[2], hipStream_t stream) {
   if (e != hipSuccess || !s.rec.valid || !s.rec.comb) return e;
   out[0] = lane_sum(s.comb.lane_settled);
   out[1] = s.comb.laddered;
+  return hipSuccess;
+}
+hipError_t strict_keymajor_stats(uint64_t out[3], hipStream_t stream) {
+  strict_counters_t s;
+  out[0] = out[1] = out[2] = 0;
+  const hipError_t e = strict_last_counters(stream, &s);
+  if (e != hipSuccess || !s.rec.valid || !s.rec.km) return e;
+  out[0] = s.km.placed;
+  out[1] = s.km.bins;
+  out[2] = s.km.slices;
   return hipSuccess;
 }
 hipError_t strict_signers_stats(uint64_t out[3], hipStream_t stream) {
@@ -1763,8 +1953,8 @@ bool strict_plan_fits(const strict_ws_t& ws, bool comb_on) {
 // One slice (items i0 .. i0 + ns) of the two-pass launch. cv is empty without the comb path.
 hipError_t strict_two_pass_slice(const strict_items_t& in, const strict_ws_t& ws,
                                  const strict_region_view& tv, const comb_region_view& cv,
-                                 const ge_niels_pad* btw, const ge_niels_pad* bcomb, uint64_t i0,
-                                 uint64_t ns) {
+                                 const km_region_view& kv, const ge_niels_pad* btw,
+                                 const ge_niels_pad* bcomb, uint64_t i0, uint64_t ns) {
   const strict_signers_t& sg = ws.signers;
   const uint64_t slice = ws.plan.slice;
   const uint32_t kcap = (uint32_t)ws.plan.key_slots, hot_cap = (uint32_t)ws.plan.hot_cap;
@@ -1817,26 +2007,46 @@ hipError_t strict_two_pass_slice(const strict_items_t& in, const strict_ws_t& ws
     e = launch_key_tables_rows(in.pks + 8 * i0, cv.hotrow, &cb->nhot, hot_cap, ks8, cv.tabs, cv.hok,
                                stream);
     if (e != hipSuccess) return e;
-    const vote_planes_t vp{tv.planes, tv.planes + 20 * slice, slice, nullptr};
+    // key-major order (kv is empty for a launch in item order): the comb kernels' lane p takes
+    // item perm[p] and leaves X' / Z' and the state at position p; the kernels up to the to-do
+    // list read them there. The sort and its readers decide alike, from *live, whether the
+    // slice is sorted.
+    const uint32_t km_min = ws.plan.km_min_live;
+    if (kv.perm) {
+      const km_keys_t kk{tv.keyslot, cv.hotidx, &cb->nhot, live, reg_on ? sg.n : 0u, hot_cap,
+                         km_min};
+      const dim3 per_chunk(grid_for(ns, kKmChunk));
+      hipLaunchKernelGGL(k_km_hist, per_chunk, lanes, 0, stream, ns, kk, kv.hist);
+      hipLaunchKernelGGL(k_km_scan, dim3(1), dim3(kKmBins), 0, stream, kv.hist, kv.cursor,
+                         kv.block, live, km_min);
+      hipLaunchKernelGGL(k_km_scatter, per_chunk, lanes, 0, stream, ns, kk, kv.cursor, kv.perm,
+                         kv.pslot);
+    }
+    const vote_planes_t vp{tv.planes, tv.planes + 20 * slice, slice, kv.perm};
     const key_tables_t hk{cv.tabs, cv.hok, tv.keyslot, ks8};
+    const km_order_t km{kv.pslot, tv.slots, km_min};
     if (reg_on)
       hipLaunchKernelGGL(in.kplane ? k_strict_keyed_signers_k : k_strict_keyed_signers, per_item,
                          lanes, 0, stream, in.msgs, in.msg_stride_words, in.pks, in.sigs, i0, ns,
                          in.status, hk, bcomb, vp, cv.hotidx, &cb->nhot, &cb->nlive, sg.tabs, sg.ok,
-                         sg.n);
+                         sg.n, km);
+    else if (in.kplane)
+      hipLaunchKernelGGL(k_strict_keyed_hot_k, per_item, lanes, 0, stream, in.msgs,
+                         in.msg_stride_words, in.pks, in.sigs, i0, ns, in.status, hk, bcomb, vp, 0,
+                         cv.hotidx, &cb->nhot, &cb->checked, km);
     else
-      hipLaunchKernelGGL(in.kplane ? k_strict_keyed_hot_k : k_strict_keyed<true>, per_item, lanes,
-                         0, stream, in.msgs, in.msg_stride_words, in.pks, in.sigs, i0, ns,
-                         in.status, hk, bcomb, vp, 0, cv.hotidx, &cb->nhot, &cb->checked);
+      hipLaunchKernelGGL((k_strict_keyed<true, km_order_t>), per_item, lanes, 0, stream, in.msgs,
+                         in.msg_stride_words, in.pks, in.sigs, i0, ns, in.status, hk, bcomb, vp, 0,
+                         cv.hotidx, &cb->nhot, &cb->checked, km);
     const uint64_t nchunks = inv_chunks(ns);
     hipLaunchKernelGGL(k_strict_keyed_inv, dim3(grid_for(nchunks, 256)), lanes, 0, stream, i0, ns,
-                       nchunks, in.status, vp, live);
+                       nchunks, in.status, vp, live, km_min);
     if (reg_on)
       hipLaunchKernelGGL(k_strict_signers_count, dim3(todo_grid(ns)), lanes, 0, stream, ns,
                          tv.keyslot, cv.hotidx, &cb->nhot, &cb->nlive, sg.n, vp.state,
-                         cb->lane_checked);
+                         cb->lane_checked, kv.perm, kv.pslot, km_min);
     hipLaunchKernelGGL(k_strict_todo_list, dim3(todo_grid(ns)), lanes, 0, stream, ns, vp.state,
-                       cv.todo, todo_count, live, (uint32_t)ws.plan.comb_decide);
+                       cv.todo, todo_count, live, (uint32_t)ws.plan.comb_decide, kv.perm, km_min);
   }
   hipLaunchKernelGGL(in.kplane ? k_strict_triage_k : k_strict_triage, per_item, lanes, 0, stream,
                      in.msgs, in.msg_stride_words, in.pks, in.sigs, i0, ns, in.status, tv.planes,
@@ -1874,17 +2084,24 @@ hipError_t launch_strict_two_pass(const strict_items_t& in, const strict_ws_t& w
   if (e == hipSuccess && cv.block)
     e = hipMemsetAsync(&cv.block->hot_keys, 0, sizeof(comb_block_t) - kCombSliceWordsBytes,
                        in.stream);
+  // key-major order of the comb path's lanes: its region (Lease::strict_ws plans none without
+  // one), the block, the histogram and the cursors cleared once per launch
+  const km_region_view kv = comb_on && p.key_major && ws.keymajor && ws.caps.km_slice >= p.slice
+                                ? km_region_view(ws.keymajor, km_region_plan(p.slice))
+                                : km_region_view();
+  if (e == hipSuccess && kv.block) e = hipMemsetAsync(kv.block, 0, kKmClearBytes, in.stream);
   if (e != hipSuccess) return e;
   int dev = 0;
   if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
     std::lock_guard<std::mutex> g(g_two_pass_m);
-    g_two_pass_last[dev] = two_pass_record_t{tv.block, cv.block, in.n, true, p.key_slots != 0};
+    g_two_pass_last[dev] =
+        two_pass_record_t{tv.block, cv.block, in.n, true, p.key_slots != 0, kv.block};
   }
   // equal slices of at most p.slice items
   const uint64_t nsl = (in.n + p.slice - 1) / p.slice;
   const uint64_t per = (in.n + nsl - 1) / nsl;
   for (uint64_t i0 = 0; i0 < in.n; i0 += per) {
-    e = strict_two_pass_slice(in, ws, tv, cv, btw, bcomb, i0, std::min(per, in.n - i0));
+    e = strict_two_pass_slice(in, ws, tv, cv, kv, btw, bcomb, i0, std::min(per, in.n - i0));
     if (e != hipSuccess) return e;
   }
   if (in.bitmap)
@@ -1927,7 +2144,7 @@ hipError_t launch_strict_keyed_fast(const strict_items_t& in, void* workspace,
                        nullptr, nullptr, nullptr);
     const uint64_t nchunks = inv_chunks(ns);
     hipLaunchKernelGGL(k_strict_keyed_inv, dim3(grid_for(nchunks, 256)), lanes, 0, stream, i0, ns,
-                       nchunks, in.status, vp, nullptr);
+                       nchunks, in.status, vp, nullptr, 0u);
     hipLaunchKernelGGL(k_strict_keyed_list, per_item, lanes, 0, stream, i0, ns, vp.state, list,
                        count);
     // the leftovers: full verification (exact status codes), the tables over the planes

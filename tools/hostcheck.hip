@@ -7,6 +7,7 @@
 #include <vector>
 #include "../narwhal_amd/csrc/nw_consts.hpp"
 #include "../narwhal_amd/csrc/nw_ladder.hpp"
+#include "../narwhal_amd/csrc/nw_strict_keymajor.hpp"
 #include "limb_ops.hpp"
 
 using namespace nw;
@@ -883,6 +884,27 @@ int hc_strict_layout(uint64_t slice, uint64_t key_slots, uint64_t hot_cap, uint6
   const int count = (int)(sizeof(v) / sizeof(v[0]));
   for (int i = 0; i < count; ++i) out[i] = v[i];
   return count;
+}
+
+// The key-major order's region (nw_strict_keymajor.hpp), for tests/test_strict_keymajor_cpu.py:
+// every offset and the bytes of km_region_plan (5 values), the bytes cleared per launch, kKmBins
+// and kKmChunk, then the offsetof of every field of km_block_t and its size (5). Returns the
+// number of values written.
+int hc_keymajor_layout(uint64_t slice, uint64_t out[]) {
+  const km_region_t r = km_region_plan(slice);
+  const uint64_t v[] = {r.hist, r.cursor, r.perm, r.pslot, r.bytes, kKmClearBytes, kKmBins, kKmChunk,
+                        offsetof(km_block_t, npos), offsetof(km_block_t, placed),
+                        offsetof(km_block_t, bins), offsetof(km_block_t, slices),
+                        sizeof(km_block_t)};
+  const int count = (int)(sizeof(v) / sizeof(v[0]));
+  for (int i = 0; i < count; ++i) out[i] = v[i];
+  return count;
+}
+// The bin of key index kk among `space` live indices (km_shift, km_bin); *shift_out = the shift.
+uint32_t hc_keymajor_bin(uint32_t kk, uint32_t space, uint32_t* shift_out) {
+  const uint32_t shift = km_shift(space);
+  if (shift_out) *shift_out = shift;
+  return km_bin(kk, space, shift);
 }
 
 }

@@ -23,7 +23,9 @@ check's verdict is not carried to the triage, every listed item takes the ladder
 --flood: every second item's message gets a flipped bit (a flood of wrong-message signatures
 under the corpus's keys: those items fail the equation under whatever key they carry).
 A library that has nw_dev_strict_decided_stats reports it for the variant's last launch
-(decided_stats: items the triage settled as equation failures, items handed to the ladder).
+(decided_stats: items the triage settled as equation failures, items handed to the ladder),
+one that has nw_dev_strict_keymajor_stats the key-major order's (keymajor_stats: items the sort
+placed, key bins used, slices sorted; LIB@NW_STRICT_KEY_MAJOR=0 / =1 turns the order off / on).
 --keys K: the corpus's signers (bench.py's config 4 has 4,096); K = 0: every item has a key
 of its own (then all items are valid: keys and signatures made on the device, no edits).
 --signers: every LIB becomes two variants of the same library and corpus, LIB#registered (the
@@ -161,6 +163,7 @@ def main():
     times = {x: [] for x in a.libs}
     ok = {}
     decided = {}
+    keymajor = {}
     for rep in range(a.reps):
         for name, L, (_, env) in zip(a.libs, libs, variants):
             if a.signers:
@@ -212,6 +215,11 @@ def main():
                 L.nw_dev_strict_decided_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
                 if L.nw_dev_strict_decided_stats(d, stream) == 0:
                     decided[name] = [int(d[0]), int(d[1])]
+            if hasattr(L, "nw_dev_strict_keymajor_stats"):
+                d = (ctypes.c_uint64 * 3)()
+                L.nw_dev_strict_keymajor_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+                if L.nw_dev_strict_keymajor_stats(d, stream) == 0:
+                    keymajor[name] = [int(d[0]), int(d[1]), int(d[2])]
     per = a.host_calls or a.steps
     if a.signers:
         for L in loaded.values():
@@ -223,7 +231,8 @@ def main():
                           "rep_medians_ms": [float(np.median(times[name][r * per:(r + 1) * per]))
                                              for r in range(a.reps)],
                           "parity": ok[name],
-                          **({"decided_stats": decided[name]} if name in decided else {})}),
+                          **({"decided_stats": decided[name]} if name in decided else {}),
+                          **({"keymajor_stats": keymajor[name]} if name in keymajor else {})}),
               flush=True)
 
 
