@@ -157,6 +157,41 @@ int nw_verify_batch_many(const uint8_t* digests, const uint8_t* pks, const uint8
                          const uint64_t* offsets, size_t nbatches, const uint8_t* z16,
                          int32_t* status_out);
 
+/* ed25519_dalek::verify_batch(messages, signatures, public_keys): every vote signs a message of
+ * its own, of any length. Vote i's message is msg_lengths[i] bytes at data + msg_offsets[i], as
+ * in nw_sha512_digest32_many (any alignment, gaps and overlaps allowed; only the referenced bytes
+ * are read, nothing for a length of 0). The checks, their order, the first-failure rule, the
+ * status codes, the failing index and z16 are exactly nw_signature_verify_batch's; the one
+ * difference is vote i's scalar k_i = SHA-512(R_i || A_i || M_i) mod l. When every vote of a
+ * batch carries the batch's 32-byte digest as its message, these entries agree with the digest
+ * entries for every batch and every coefficient set. A kernel first computes every vote's k, one
+ * lane per vote (a wave runs as long as its longest message, so the entries are meant for messages
+ * of up to a few KB: transactions, not blobs); the batch kernels then read k instead of hashing:
+ * Straus chunks, Pippenger above NW_BATCH_PIPPENGER_MIN votes, slices, under the same NW_BATCH_*
+ * knobs. A lone large batch runs the separate Pippenger kernels here, never the digest entry's
+ * fused launches (which hash the batch digest in the kernel). The registered signers
+ * (nw_strict_signers_set) serve these entries as they serve nw_verify_batch_many, under the same
+ * NW_BATCH_SIGNERS* knobs and counted by the same nw_batch_signers_stats /
+ * nw_batch_signers_vote_stats. Not served: the certificate paths and committee key tables, and
+ * the aggregation service (a per-message batch request of nw_service_* is a follow-up).
+ * n == 0 is Ok. Under nw_set_device(NW_ALL_DEVICES) each device gets one contiguous part of
+ * whole batches with its votes, message ranges and z16. */
+int nw_signature_verify_batch_msgs(const uint8_t* data, const uint64_t* msg_offsets,
+                                   const uint64_t* msg_lengths, const uint8_t* pks,
+                                   const uint8_t* sigs, size_t n, const uint8_t* z16,
+                                   size_t* fail_index);
+
+/* nbatches independent such calls. Batch b = votes [offsets[b], offsets[b+1]) of pks / sigs /
+ * msg_offsets / msg_lengths (and z16 if given): msg_offsets and msg_lengths have one entry per
+ * vote, offsets[nbatches] in all. status_out: nbatches x int32; fail_index_out (optional):
+ * nbatches x uint64, the failing vote within its batch, or the batch's size for the equation.
+ * nbatches == 0 is Ok, and so is an empty batch. */
+int nw_verify_batch_msgs_many(const uint8_t* data, const uint64_t* msg_offsets,
+                              const uint64_t* msg_lengths, const uint8_t* pks,
+                              const uint8_t* sigs, const uint64_t* offsets, size_t nbatches,
+                              const uint8_t* z16, int32_t* status_out,
+                              uint64_t* fail_index_out);
+
 /* crypto::generate_keypair given the CSPRNG's 32-byte seeds (crypto/src/lib.rs:167-175:
  * dalek Keypair::generate fills the seed from the RNG): pks_out n x 32 bytes. The
  * crypto::SecretKey bytes are seed || pk. */
@@ -195,6 +230,13 @@ int nw_submit_verify_strict_msgs(const uint8_t* data, const uint64_t* offsets,
 int nw_submit_verify_batch_many(const uint8_t* digests, const uint8_t* pks, const uint8_t* sigs,
                                 const uint64_t* offsets, size_t nbatches, const uint8_t* z16,
                                 int32_t* status_out, uint64_t* fail_index_out, nw_job** job);
+/* verify_batch over per-vote messages (as nw_verify_batch_msgs_many; the referenced message
+ * bytes are packed contiguously at submit). */
+int nw_submit_verify_batch_msgs(const uint8_t* data, const uint64_t* msg_offsets,
+                                const uint64_t* msg_lengths, const uint8_t* pks,
+                                const uint8_t* sigs, const uint64_t* offsets, size_t nbatches,
+                                const uint8_t* z16, int32_t* status_out,
+                                uint64_t* fail_index_out, nw_job** job);
 /* Digest(Sha512(m)[..32]) (as nw_sha512_digest32_many). */
 int nw_submit_sha512_digest32_many(const uint8_t* data, const uint64_t* offsets,
                                    const uint64_t* lengths, size_t n, uint8_t* out32,
@@ -297,8 +339,11 @@ int nw_dev_strict_keymajor_stats(uint64_t out[3], void* stream);
  * the set. NW_BATCH_SIGNERS=0 turns this off, NW_BATCH_SIGNERS_MIN_VOTES (default 1) is the
  * smallest call that takes it (both read per call; NW_STRICT_COMB does not govern it). It needs
  * the device's B comb table: where that cannot be allocated the calls run as without a set.
- * Not served: nw_dev_verify_batch_many (the caller owns the workspace) and the Header / Vote /
- * Certificate entries, which have their committee's tables. */
+ * The per-message entries (nw_signature_verify_batch_msgs, nw_verify_batch_msgs_many,
+ * nw_submit_verify_batch_msgs) are served alike: the comb check reads each vote's k from the
+ * call's plane.
+ * Not served: nw_dev_verify_batch_many and nw_dev_verify_batch_msgs_many (the caller owns the
+ * workspace) and the Header / Vote / Certificate entries, which have their committee's tables. */
 int nw_strict_signers_set(const uint8_t* pks, size_t n);
 /* Registered keys on the current device. */
 int nw_strict_signers_count(uint64_t* n);
@@ -553,6 +598,20 @@ int nw_dev_verify_batch_many(const void* digests, const void* pks, const void* s
                              const uint8_t* zkey32, void* workspace, int32_t* status_out,
                              uint64_t* fail_index, void* stream);
 
+/* Device form of nw_verify_batch_msgs_many: data, msg_offsets, msg_lengths (one entry per vote),
+ * pks, sigs, offsets, z16, status_out and fail_index are device pointers, host_offsets and zkey32
+ * as in nw_dev_verify_batch_many. workspace: nw_dev_verify_batch_msgs_workspace bytes of device
+ * memory, the batch workspace followed by the plane of every vote's k (32 bytes per vote). The
+ * plane is the caller's, so calls on different streams with workspaces of their own do not meet.
+ * The registered signers do not serve this entry (the caller owns the workspace). */
+size_t nw_dev_verify_batch_msgs_workspace(size_t nbatches, size_t nitems);
+int nw_dev_verify_batch_msgs_many(const void* data, const uint64_t* msg_offsets,
+                                  const uint64_t* msg_lengths, const void* pks, const void* sigs,
+                                  const uint64_t* offsets, const uint64_t* host_offsets,
+                                  size_t nbatches, size_t nitems, const void* z16,
+                                  const uint8_t* zkey32, void* workspace, int32_t* status_out,
+                                  uint64_t* fail_index, void* stream);
+
 /* Device form of nw_certificates_verify_many: every pointer inside *committee and *certs
  * (and z16, status_out, index_out, workspace) is a device pointer; the structs themselves
  * are host memory. header_bytes_len and nvotes must be set. headers_only != 0 runs
@@ -578,6 +637,11 @@ int nw_host_verify_strict_msgs_many(const uint8_t* data, const uint64_t* offsets
 int nw_host_verify_batch_many(const uint8_t* digests, const uint8_t* pks, const uint8_t* sigs,
                               const uint64_t* offsets, size_t nbatches, const uint8_t* z16,
                               int32_t* status_out, uint64_t* fail_index_out);
+int nw_host_verify_batch_msgs_many(const uint8_t* data, const uint64_t* msg_offsets,
+                                   const uint64_t* msg_lengths, const uint8_t* pks,
+                                   const uint8_t* sigs, const uint64_t* offsets, size_t nbatches,
+                                   const uint8_t* z16, int32_t* status_out,
+                                   uint64_t* fail_index_out);
 int nw_host_certificates_verify_many(const nw_committee* committee, const nw_certificates* certs,
                                      const uint8_t* z16, int headers_only, int32_t* status_out,
                                      uint64_t* index_out);

@@ -60,6 +60,12 @@ def prototypes() -> dict:
         "nw_host_verify_strict_msgs_many": ([P, P, P, P, P, S, P], I),
         "nw_signature_verify_batch": ([P, P, P, S, P, ctypes.POINTER(S)], I),
         "nw_verify_batch_many": ([P, P, P, P, S, P, P], I),
+        "nw_signature_verify_batch_msgs": ([P, P, P, P, P, S, P, ctypes.POINTER(S)], I),
+        "nw_verify_batch_msgs_many": ([P, P, P, P, P, P, S, P, P, P], I),
+        "nw_submit_verify_batch_msgs": ([P, P, P, P, P, P, S, P, P, P, ctypes.POINTER(P)], I),
+        "nw_dev_verify_batch_msgs_workspace": ([S, S], S),
+        "nw_dev_verify_batch_msgs_many": ([P, P, P, P, P, P, P, S, S, P, P, P, P, P, P], I),
+        "nw_host_verify_batch_msgs_many": ([P, P, P, P, P, P, S, P, P, P], I),
         "nw_dev_sha512_digest32_many": ([P, P, P, S, P, P], I),
         "nw_dev_verify_strict_many": ([P, S, P, P, S, P, P, P], I),
         "nw_dev_strict_keyset_stats": ([P, P], I),

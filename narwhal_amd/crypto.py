@@ -10,12 +10,13 @@ behaviour, so code (and tests) written against the Rust crate read the same here
     Signature.verify(digest, pk)          lib.rs:200-204  -> raises CryptoError
     Signature.verify_batch(digest, votes) lib.rs:206-219  -> raises CryptoError
     Signature.verify_message(msg, pk)     dalek's verify_strict(&[u8]): a message of any length
+    Signature.verify_batch_messages(items) dalek's verify_batch(messages, signatures, keys)
     CryptoError                           lib.rs:18 (ed25519::Error, opaque)
 
 Every check runs in the gfx950 kernels through the C ABI (include/narwhal_amd.h); there
 is no CPU path. Runtime/device failures raise EngineError, never CryptoError.
 Bulk helpers (verify_strict_many, verify_strict_msgs_many, verify_batch_many,
-sha512_digest32_many) expose the
+verify_batch_msgs_many, sha512_digest32_many) expose the
 batched entry points the aggregation service uses.
 """
 from __future__ import annotations
@@ -34,7 +35,7 @@ __all__ = ["Digest", "Hash", "PublicKey", "SecretKey", "Signature", "CryptoError
            "EngineError", "generate_keypair", "keypair_from_seed_many", "sign_many",
            "sha512_digest", "sha512_digest32_many", "verify_strict_many",
            "verify_strict_msgs_many",
-           "verify_batch_many", "set_strict_signers", "strict_signers_count",
+           "verify_batch_many", "verify_batch_msgs_many", "set_strict_signers", "strict_signers_count",
            "strict_signers_stats", "batch_signers_stats",
            "batch_signers_vote_stats"]
 
@@ -213,6 +214,25 @@ class Signature:
         if rc != _lib.NW_OK:
             raise CryptoError(rc, idx.value)
 
+    @staticmethod
+    def verify_batch_messages(items: Iterable[tuple[bytes, PublicKey, "Signature"]],
+                              z16: bytes | None = None) -> None:
+        """ed25519_dalek::verify_batch(messages, signatures, public_keys): every item signs a
+        message of its own, of any length (empty -> Ok). Raises CryptoError(code, index) like
+        verify_batch; z16 injects the coefficients (n x 16 bytes) for deterministic tests."""
+        items = list(items)
+        n = len(items)
+        if n == 0:
+            return
+        st, fi = verify_batch_msgs_many(
+            [bytes(m) for m, _, _ in items],
+            np.frombuffer(b"".join(pk.value for _, pk, _ in items), np.uint8),
+            np.frombuffer(b"".join(s.flatten() for _, _, s in items), np.uint8),
+            np.array([0, n], np.uint64),
+            None if z16 is None else np.frombuffer(bytes(z16), np.uint8))
+        if st[0] != _lib.NW_OK:
+            raise CryptoError(int(st[0]), int(fi[0]))
+
 
 def _cbuf(b: bytes):
     return ctypes.c_char_p(bytes(b)) if b else ctypes.c_char_p(b"\0")
@@ -291,6 +311,68 @@ def verify_strict_msgs_many(messages, pks: np.ndarray,
                                                     _ptr(pks), _ptr(sigs), n, _ptr(st), _ptr(bm)),
               "nw_verify_strict_msgs_many")
     return st, bm
+
+
+def _message_arrays(messages):
+    """(data, offsets, lengths) of a list of bytes, or of the triple itself."""
+    if isinstance(messages, tuple):
+        data, offsets, lengths = messages
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lengths = np.ascontiguousarray(lengths, dtype=np.uint64)
+    else:
+        raw = [bytes(m) for m in messages]
+        lengths = np.array([len(m) for m in raw], dtype=np.uint64)
+        offsets = np.zeros(len(raw), dtype=np.uint64)
+        if len(raw) > 1:
+            offsets[1:] = np.cumsum(lengths)[:-1]
+        data = np.frombuffer(b"".join(raw), np.uint8)
+    # every message inside the caller's data, before an empty array gets its one byte to point
+    # at; offset + length is never formed (a 64-bit sum could wrap)
+    size = np.uint64(data.size)
+    if len(offsets) == len(lengths):
+        room = size - np.minimum(offsets, size)
+        if bool(((lengths > 0) & ((offsets > size) | (lengths > room))).any()):
+            raise ValueError("a message lies outside data")
+    if data.size == 0:
+        data = np.zeros(1, np.uint8)
+    return data, offsets, lengths
+
+
+def verify_batch_msgs_many(messages, pks: np.ndarray, sigs: np.ndarray, offsets: np.ndarray,
+                           z16: np.ndarray | None = None) -> tuple[np.ndarray, np.ndarray]:
+    """Bulk verify_batch over per-vote messages of any length (nw_verify_batch_msgs_many): batch
+    b = votes offsets[b]..offsets[b+1], vote i signs its own message. ``messages`` is a list of
+    bytes (one per vote), or the (data, offsets, lengths) arrays as in verify_strict_msgs_many.
+    Returns (status int32[nb], fail_index uint64[nb]): the failing vote within its batch, or
+    the batch's size for the equation."""
+    data, moffs, mlens = _message_arrays(messages)
+    pks = np.ascontiguousarray(pks, dtype=np.uint8).reshape(-1, 32)
+    sigs = np.ascontiguousarray(sigs, dtype=np.uint8).reshape(-1, 64)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+    n = pks.shape[0]
+    nb = max(len(offsets) - 1, 0)
+    if len(moffs) != n or len(mlens) != n or sigs.shape[0] != n:
+        raise ValueError("messages, pks and sigs must name the same number of votes")
+    if len(offsets) == 0:
+        if n:
+            raise ValueError("offsets must run from 0 to the number of votes")
+    elif (int(offsets[0]) != 0 or int(offsets[-1]) != n
+          or (nb and bool((offsets[1:] < offsets[:-1]).any()))):
+        raise ValueError("offsets must run from 0 to the number of votes")
+    zp = None
+    if z16 is not None:
+        z16 = np.ascontiguousarray(z16, dtype=np.uint8).reshape(-1)
+        if z16.size != 16 * n:
+            raise ValueError("z16 holds 16 bytes per vote")
+        zp = _ptr(z16) if n else None
+    st = np.zeros(nb, dtype=np.int32)
+    fi = np.zeros(nb, dtype=np.uint64)
+    if nb:
+        check(_lib.lib().nw_verify_batch_msgs_many(_ptr(data), _ptr(moffs), _ptr(mlens), _ptr(pks),
+                                                   _ptr(sigs), _ptr(offsets), nb, zp, _ptr(st),
+                                                   _ptr(fi)), "nw_verify_batch_msgs_many")
+    return st, fi
 
 
 def set_strict_signers(keys) -> None:

@@ -560,6 +560,50 @@ int nw_dev_verify_batch_many(const void* digests, const void* pks, const void* s
   return 0;
 }
 
+// The batch workspace, then the call's k plane (32 bytes per vote) at the next 256-byte boundary.
+static size_t batch_msgs_plane_offset(size_t nbatches, size_t nitems) {
+  return (nw::batch_workspace_bytes(nbatches, nitems) + 255) & ~(size_t)255;
+}
+
+size_t nw_dev_verify_batch_msgs_workspace(size_t nbatches, size_t nitems) {
+  return batch_msgs_plane_offset(nbatches, nitems) + 32 * nitems;
+}
+
+int nw_dev_verify_batch_msgs_many(const void* data, const uint64_t* msg_offsets,
+                                  const uint64_t* msg_lengths, const void* pks, const void* sigs,
+                                  const uint64_t* offsets, const uint64_t* host_offsets,
+                                  size_t nbatches, size_t nitems, const void* z16,
+                                  const uint8_t* zkey32, void* workspace, int32_t* status_out,
+                                  uint64_t* fail_index, void* stream) {
+  DevCtx* c;
+  int rc = begin(&c);
+  if (rc) return rc;
+  if (nbatches == 0) return 0;
+  // data may be null when every message is empty: nothing is read through it then
+  if (!offsets || !workspace || !status_out ||
+      (nitems && (!msg_offsets || !msg_lengths || !pks || !sigs)))
+    return set_err(NW_E_INVALID_ARG, "null pointer");
+  nw::z_key_t key;
+  rc = fill_key(key, zkey32);
+  if (rc) return rc;
+  hipStream_t s = pick_stream(stream, c);
+  std::vector<uint64_t> tmp;
+  const uint64_t* ho;
+  rc = host_offsets_of(offsets, host_offsets, nbatches, s, tmp, &ho);
+  if (rc) return rc;
+  if (ho[0] != 0 || ho[nbatches] != nitems)
+    return set_err(NW_E_INVALID_ARG, "offsets must run from 0 to nitems");
+  uint32_t* const kplane = reinterpret_cast<uint32_t*>(
+      static_cast<char*>(workspace) + batch_msgs_plane_offset(nbatches, nitems));
+  NW_HIP(nw::launch_verify_batch_msgs(static_cast<const uint8_t*>(data), msg_offsets, msg_lengths,
+                                      offsets, ho, nbatches, static_cast<const uint32_t*>(pks),
+                                      static_cast<const uint32_t*>(sigs), nitems,
+                                      static_cast<const uint32_t*>(z16), key, workspace, kplane,
+                                      false, status_out, fail_index, s),
+         "verify_batch launch over messages");
+  return 0;
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------

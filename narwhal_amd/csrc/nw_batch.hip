@@ -304,6 +304,13 @@ __global__ __launch_bounds__(256) void k_bv_expand(const uint64_t* __restrict__ 
 
 // ------------------------------------------------------------------------------ items
 // Item gi (slot li = gi - i0) of batch lo: flags, scalars and the R (and A) tables.
+// kPlane (launch_verify_batch_msgs): `digests` is the call's k plane, k_i = SHA-512(R_i || A_i ||
+// M_i) mod l already there (k_strict_hram) at 8 words per vote, indexed by the call-global vote
+// index gi (not by the batch, the slice or a list position): eight loads, no hash, no reduction.
+// The instances over the plane are kernels of their own (k_bv_items_k, k_bv_items_listed_k,
+// k_pip_points_k), so those over the digests keep their code objects. Not built over the plane:
+// k_bv_items_chunked (certificate callers only), the certificate groups, the keyed path.
+template <bool kPlane = false>
 __device__ __forceinline__ void bv_item_build(
     uint64_t gi, uint64_t li, uint64_t lo, const uint32_t* __restrict__ digests,
     const uint32_t* __restrict__ pks, const uint32_t* __restrict__ sigs,
@@ -316,7 +323,7 @@ __device__ __forceinline__ void bv_item_build(
     Aw[j] = pks[8 * gi + j];
     Rw[j] = sigs[16 * gi + j];
     Sw[j] = sigs[16 * gi + 8 + j];
-    Mw[j] = digests[8 * lo + j];
+    Mw[j] = digests[8 * (kPlane ? gi : lo) + j];
   }
   uint32_t flags = 0;
   if ((Sw[7] >> 29) != 0) flags |= BF_S_HIGH;
@@ -324,10 +331,15 @@ __device__ __forceinline__ void bv_item_build(
 #pragma unroll
   for (int j = 0; j < 8; ++j) s.w[j] = Sw[j];
   if (!sc_is_canonical(s)) flags |= BF_S_NONCANON;
-  uint32_t hx[16];
-  hram96(hx, Rw, Aw, Mw);
   sc k;
-  sc_reduce512(k, hx);
+  if constexpr (kPlane) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) k.w[j] = Mw[j];
+  } else {
+    uint32_t hx[16];
+    hram96(hx, Rw, Aw, Mw);
+    sc_reduce512(k, hx);
+  }
   uint32_t zw[4];
   if (z16) {
 #pragma unroll
@@ -412,6 +424,25 @@ __global__ __launch_bounds__(256) void k_bv_items(
   bv_item_build(gi, gi - i0, lo, digests, pks, sigs, z16, zkey, items, tabs, keys);
 }
 
+// k_bv_items over the call's k plane (bv_item_build<true>): plain batches only, no key tables.
+__global__ __launch_bounds__(256) void k_bv_items_k(
+    const uint32_t* __restrict__ kplane, const uint64_t* __restrict__ offsets, uint64_t b0,
+    uint64_t b1, uint64_t i0, uint64_t i1, uint32_t pmin, const uint32_t* __restrict__ pks,
+    const uint32_t* __restrict__ sigs, const uint32_t* __restrict__ z16, z_key_t zkey,
+    bv_item* __restrict__ items, ge_cached* __restrict__ tabs, batch_skip_t sk) {
+  const uint64_t gi = i0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gi >= i1) return;
+  uint64_t lo = b0, hi = b1;
+  while (hi - lo > 1) {
+    const uint64_t mid = (lo + hi) >> 1;
+    if (offsets[mid] <= gi) lo = mid; else hi = mid;
+  }
+  if (offsets[lo + 1] - offsets[lo] >= pmin) return;   // k_pip_points_k
+  if (skipped(sk, lo)) return;
+  bv_item_build<true>(gi, gi - i0, lo, kplane, pks, sigs, z16, zkey, items, tabs,
+                      key_tables_t{nullptr, nullptr, nullptr, {}});
+}
+
 // The same items driven by the chunk list (k_bv_expand): lane = chunk * C + j. When a skip
 // list leaves only a few scattered batches to run (launch_votes_keyed's failed
 // certificates), a lane per vote would leave most waves with one or two live lanes each
@@ -456,6 +487,30 @@ __global__ __launch_bounds__(256) void k_bv_items_listed(
   if (offsets[lo + 1] - offsets[lo] >= pmin) return;   // k_pip_points
   bv_item_build(gi, gi - i0, lo, digests, pks, sigs, z16, zkey, items, tabs,
                 key_tables_t{nullptr, nullptr, nullptr, {}});
+}
+
+// k_bv_items_listed over the call's k plane: the list's entries are call-global vote indices,
+// which is what the plane is indexed by.
+__global__ __launch_bounds__(256) void k_bv_items_listed_k(
+    const uint32_t* __restrict__ list, const uint32_t* __restrict__ count,
+    const uint32_t* __restrict__ kplane, const uint64_t* __restrict__ offsets, uint64_t b0,
+    uint64_t b1, uint64_t i0, uint64_t i1, uint32_t pmin, const uint32_t* __restrict__ pks,
+    const uint32_t* __restrict__ sigs, const uint32_t* __restrict__ z16, z_key_t zkey,
+    bv_item* __restrict__ items, ge_cached* __restrict__ tabs) {
+  const uint32_t nl = *count;
+  if (blockIdx.x * blockDim.x >= nl) return;
+  const uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= nl) return;
+  const uint64_t gi = list[l];
+  if (gi < i0 || gi >= i1) return;
+  uint64_t lo = b0, hi = b1;
+  while (hi - lo > 1) {
+    const uint64_t mid = (lo + hi) >> 1;
+    if (offsets[mid] <= gi) lo = mid; else hi = mid;
+  }
+  if (offsets[lo + 1] - offsets[lo] >= pmin) return;   // k_pip_points_k
+  bv_item_build<true>(gi, gi - i0, lo, kplane, pks, sigs, z16, zkey, items, tabs,
+                      key_tables_t{nullptr, nullptr, nullptr, {}});
 }
 
 // One lane per chunk of the plan: a chunk that holds a listed vote (state != kVotePass) goes
@@ -917,7 +972,9 @@ __device__ __forceinline__ void pip_point_neutral(int which, bv_item* it, const 
 // kVotes (plain batches after the comb phase): a vote whose vstate is kVotePass is neutral, as
 // a vote of a certificate decided before the votes is in group mode; neither of its points is
 // decompressed.
-template <bool kVotes>
+// kPlane (launch_verify_batch_msgs, plain batches only): `digests` is the call's k plane and
+// role 0 loads k from its row gi, the call-global vote index, instead of hashing (bv_item_build).
+template <bool kVotes, bool kPlane = false>
 __device__ __forceinline__ void pip_point_do(
     int which, uint64_t li, const uint32_t* __restrict__ digests,
     const uint64_t* __restrict__ offsets, uint64_t b0, uint64_t b1, uint64_t i0, uint64_t i1,
@@ -977,7 +1034,7 @@ __device__ __forceinline__ void pip_point_do(
     Aw[j] = pks[8 * gi + j];
     Rw[j] = sigs[16 * gi + j];
     Sw[j] = sigs[16 * gi + 8 + j];
-    Mw[j] = digests[8 * dig + j];
+    Mw[j] = digests[8 * (kPlane ? gi : dig) + j];
   }
   uint32_t flags = 0;
   if ((Sw[7] >> 29) != 0) flags |= BF_S_HIGH;
@@ -985,10 +1042,15 @@ __device__ __forceinline__ void pip_point_do(
 #pragma unroll
   for (int j = 0; j < 8; ++j) s.w[j] = Sw[j];
   if (!sc_is_canonical(s)) flags |= BF_S_NONCANON;
-  uint32_t hx[16];
-  hram96(hx, Rw, Aw, Mw);
   sc k;
-  sc_reduce512(k, hx);
+  if constexpr (kPlane) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) k.w[j] = Mw[j];
+  } else {
+    uint32_t hx[16];
+    hram96(hx, Rw, Aw, Mw);
+    sc_reduce512(k, hx);
+  }
   uint32_t zw[4];
   if (z16) {
 #pragma unroll
@@ -1045,6 +1107,20 @@ __global__ __launch_bounds__(256, 3) void k_pip_points(
   pip_point_do<kVotes>((int)(role0 + wave % roles), (wave / roles) * 64 + (g & 63), digests,
                        offsets, b0, b1, i0, i1, pmin, pks, sigs, z16, zkey, items, tabs, grp, sk,
                        vstate);
+}
+
+// k_pip_points over the call's k plane (pip_point_do<kVotes, true>): plain batches, three roles.
+template <bool kVotes>
+__global__ __launch_bounds__(256, 3) void k_pip_points_k(
+    const uint32_t* __restrict__ kplane, const uint64_t* __restrict__ offsets, uint64_t b0,
+    uint64_t b1, uint64_t i0, uint64_t i1, uint32_t pmin, const uint32_t* __restrict__ pks,
+    const uint32_t* __restrict__ sigs, const uint32_t* __restrict__ z16, z_key_t zkey,
+    bv_item* __restrict__ items, ge_cached* __restrict__ tabs, batch_skip_t sk,
+    const uint32_t* __restrict__ vstate) {
+  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, wave = g >> 6;
+  pip_point_do<kVotes, true>((int)(wave % 3), (wave / 3) * 64 + (g & 63), kplane, offsets, b0, b1,
+                             i0, i1, pmin, pks, sigs, z16, zkey, items, tabs, pip_group_t{}, sk,
+                             vstate);
 }
 
 // Group mode: per group, sum_i c_i per committee key (LDS, 64-bit limb sums), reduced mod l,
@@ -2464,14 +2540,19 @@ hipError_t launch_pip(const uint32_t* digests, const uint64_t* offsets, uint64_t
                 const pip_group_t& grp, hipStream_t stream,
                 uint32_t* fctr, const input_gate_t* gate = nullptr, uint32_t* done = nullptr,
                 uint32_t done_seq = 0, const batch_skip_t& sk = batch_skip_t{nullptr, 1},
-                const uint32_t* pip_count = nullptr, const uint32_t* vstate = nullptr) {
+                const uint32_t* pip_count = nullptr, const uint32_t* vstate = nullptr,
+                bool kplane = false) {
   const bool group = grp.cert_vote_offsets != nullptr;
+  // over the k plane (`digests` is the plane): plain batches, and never the fused launches
+  // (k_pip_points_sorted hashes the batch digest itself and the input gate belongs to it; the
+  // fused tail is not taken behind the unfused head either, it stays the digest entry's)
+  if (kplane && (group || gate || done)) return hipErrorInvalidValue;
   const uint32_t extra = group ? grp.nkeys : 0;   // key sums
   const uint32_t roles = group ? 2 : 3;
   const uint64_t wv = (i1 - i0 + 63) / 64;   // waves per role
   // one large batch alone in its slice (config 1's call): the fused head and tail
   const bool fused = pip_fuse_on() && !group && npip == 1 && e - b == 1 && pmax >= kFuseMinN &&
-                     pmax <= kFuseMaxN && npip <= pip_win_lp_max() && !pip_count;
+                     pmax <= kFuseMaxN && npip <= pip_win_lp_max() && !pip_count && !kplane;
   const bool fuse_head = fused && pip_fuse_head_on();
   if (fuse_head) {
     // one large batch alone (config 1's call): points and sorts in one launch
@@ -2486,7 +2567,13 @@ hipError_t launch_pip(const uint32_t* digests, const uint64_t* offsets, uint64_t
                        gate ? *gate : input_gate_t{nullptr, 0u, 64u});
   } else {
     const dim3 gp((unsigned)((wv * roles * 64 + 255) / 256));
-    if (vstate)
+    if (kplane && vstate)
+      hipLaunchKernelGGL(k_pip_points_k<true>, gp, dim3(256), 0, stream, digests, offsets, b, e,
+                         i0, i1, pmin, pks, sigs, z16, zkey, w.items, w.tabs, sk, vstate);
+    else if (kplane)
+      hipLaunchKernelGGL(k_pip_points_k<false>, gp, dim3(256), 0, stream, digests, offsets, b, e,
+                         i0, i1, pmin, pks, sigs, z16, zkey, w.items, w.tabs, sk, nullptr);
+    else if (vstate)
       hipLaunchKernelGGL(k_pip_points<true>, gp, dim3(256), 0, stream, digests, offsets, b, e, i0,
                          i1, pmin, pks, sigs, z16, zkey, w.items, w.tabs, grp, roles, 0u, sk,
                          vstate);
@@ -2570,18 +2657,23 @@ __global__ __launch_bounds__(256) void k_grp_setup(const uint64_t* __restrict__ 
   }
 }
 
-}  // namespace
-
-hipError_t launch_verify_batch(const uint32_t* digests, const uint64_t* offsets,
-                               const uint64_t* host_offsets, uint64_t nbatches,
-                               const uint32_t* pks, const uint32_t* sigs, uint64_t nitems,
-                               const uint32_t* z16, const z_key_t& zkey, void* workspace,
-                               int32_t* status, uint64_t* fail_index, hipStream_t stream,
-                               const key_tables_t* keys, const uint32_t* skip_group_ok,
-                               uint64_t skip_per_group, double active_frac,
-                               uint32_t* fuse_ctr, const input_gate_t* gate,
-                               uint32_t* done, uint32_t done_seq, bool skip_pip,
-                               const batch_votes_t* votes) {
+// launch_verify_batch's sequence. kplane (launch_verify_batch_msgs): `digests` is the call's k
+// plane, 8 words per vote, and the item and point kernels are their plane instances; plain
+// batches only (no key tables, no certificate skip list's compacted items), never the fused
+// launches.
+hipError_t verify_batch_run(const uint32_t* digests, const uint64_t* offsets,
+                            const uint64_t* host_offsets, uint64_t nbatches,
+                            const uint32_t* pks, const uint32_t* sigs, uint64_t nitems,
+                            const uint32_t* z16, const z_key_t& zkey, void* workspace,
+                            int32_t* status, uint64_t* fail_index, hipStream_t stream,
+                            const key_tables_t* keys, const uint32_t* skip_group_ok,
+                            uint64_t skip_per_group, double active_frac,
+                            uint32_t* fuse_ctr, const input_gate_t* gate,
+                            uint32_t* done, uint32_t done_seq, bool skip_pip,
+                            const batch_votes_t* votes, bool kplane) {
+  if (kplane && (keys || fuse_ctr || gate || done || active_frac < 1.0 ||
+                 (skip_group_ok && !skip_pip)))
+    return hipErrorInvalidValue;
   // Pippenger batches under a skip list take the separate kernels only (launch_pip)
   if (skip_pip && (!skip_group_ok || fuse_ctr || gate || done)) return hipErrorInvalidValue;
   // the comb phase's vote list: its callers' plain batches only (a vote's state says nothing
@@ -2676,7 +2768,11 @@ hipError_t launch_verify_batch(const uint32_t* digests, const uint64_t* offsets,
     }
     if (votes) {
       // the items of the listed votes: the grid is the host's bound, every vote of the call
-      if (chunks)
+      if (chunks && kplane)
+        hipLaunchKernelGGL(k_bv_items_listed_k, dim3((unsigned)((nitems + 255) / 256)),
+                           dim3(256), 0, stream, votes->list, votes->count, digests, offsets, b, e,
+                           i0, i1, pmin, pks, sigs, z16, zkey, w.items, w.tabs);
+      else if (chunks)
         hipLaunchKernelGGL(k_bv_items_listed, dim3((unsigned)((nitems + 255) / 256)), dim3(256),
                            0, stream, votes->list, votes->count, digests, offsets, b, e, i0, i1,
                            pmin, pks, sigs, z16, zkey, w.items, w.tabs);
@@ -2685,6 +2781,10 @@ hipError_t launch_verify_batch(const uint32_t* digests, const uint64_t* offsets,
                          dim3(256), 0, stream, w.chunks, (uint32_t)chunks,
                          w.chunk_start + (e - b), C, digests, b, i0, pks, sigs, z16, zkey,
                          w.items, w.tabs, kt);
+    else if (i1 > i0 && npip != e - b && !compact && kplane)
+      hipLaunchKernelGGL(k_bv_items_k, dim3((unsigned)((i1 - i0 + 255) / 256)), dim3(256), 0,
+                         stream, digests, offsets, b, e, i0, i1, pmin, pks, sigs, z16, zkey,
+                         w.items, w.tabs, sk);
     else if (i1 > i0 && npip != e - b && !compact)
       hipLaunchKernelGGL(k_bv_items, dim3((unsigned)((i1 - i0 + 255) / 256)), dim3(256), 0,
                          stream, digests, offsets, b, e, i0, i1, pmin, pks, sigs, z16, zkey,
@@ -2694,7 +2794,7 @@ hipError_t launch_verify_batch(const uint32_t* digests, const uint64_t* offsets,
                                        sigs, z16, zkey, w, status, fail_index, nogrp, stream,
                                        own_ctr ? fuse_ctr : w.chunk_start, gate, done,
                                        done_seq, sk, pip_count,
-                                       votes ? votes->state : nullptr);
+                                       votes ? votes->state : nullptr, kplane);
       if (pe != hipSuccess) return pe;
     }
     if (chunks && votes)
@@ -2717,6 +2817,48 @@ hipError_t launch_verify_batch(const uint32_t* digests, const uint64_t* offsets,
     b = e;
   }
   return hipSuccess;
+}
+
+}  // namespace
+
+hipError_t launch_verify_batch(const uint32_t* digests, const uint64_t* offsets,
+                               const uint64_t* host_offsets, uint64_t nbatches,
+                               const uint32_t* pks, const uint32_t* sigs, uint64_t nitems,
+                               const uint32_t* z16, const z_key_t& zkey, void* workspace,
+                               int32_t* status, uint64_t* fail_index, hipStream_t stream,
+                               const key_tables_t* keys, const uint32_t* skip_group_ok,
+                               uint64_t skip_per_group, double active_frac,
+                               uint32_t* fuse_ctr, const input_gate_t* gate,
+                               uint32_t* done, uint32_t done_seq, bool skip_pip,
+                               const batch_votes_t* votes) {
+  return verify_batch_run(digests, offsets, host_offsets, nbatches, pks, sigs, nitems, z16, zkey,
+                          workspace, status, fail_index, stream, keys, skip_group_ok,
+                          skip_per_group, active_frac, fuse_ctr, gate, done, done_seq, skip_pip,
+                          votes, false);
+}
+
+hipError_t launch_verify_batch_msgs(const uint8_t* data, const uint64_t* msg_offsets,
+                                    const uint64_t* msg_lengths, const uint64_t* offsets,
+                                    const uint64_t* host_offsets, uint64_t nbatches,
+                                    const uint32_t* pks, const uint32_t* sigs, uint64_t nitems,
+                                    const uint32_t* z16, const z_key_t& zkey, void* workspace,
+                                    uint32_t* kplane, bool hashed, int32_t* status,
+                                    uint64_t* fail_index, hipStream_t stream,
+                                    const uint32_t* skip_group_ok, const batch_votes_t* votes,
+                                    uint32_t* fuse_ctr, const input_gate_t* gate, uint32_t* done) {
+  // the fused launches hash the batch digest in the kernel: not for a call over the plane
+  if (fuse_ctr || gate || done) return hipErrorInvalidValue;
+  if (nbatches == 0) return hipSuccess;
+  if (nitems && !kplane) return hipErrorInvalidValue;
+  if (!hashed) {
+    const hipError_t he =
+        launch_strict_hram(data, msg_offsets, msg_lengths, pks, sigs, nitems, kplane, stream);
+    if (he != hipSuccess) return he;
+  }
+  return verify_batch_run(kplane, offsets, host_offsets, nbatches, pks, sigs, nitems, z16, zkey,
+                          workspace, status, fail_index, stream, nullptr, skip_group_ok,
+                          skip_group_ok ? 1 : 0, 1.0, nullptr, nullptr, nullptr, 0,
+                          skip_group_ok != nullptr, votes, true);
 }
 
 size_t verify_batch_fuse_ctr_bytes() { return 4ull * kFuseCtr; }

@@ -490,8 +490,12 @@ bool votes_pass(const Committee& com, const uint8_t digest[32], const uint8_t* p
 // dalek verify_batch, every step: per vote s high bits / A decode (first failure), s < l over
 // all, R decode over all, then sum z_i R_i + (z_i k_i mod l) A_i - (sum z_i s_i mod l) B ==
 // identity, by a Straus ladder (4-bit signed windows over 9-entry tables, 8-bit B digits).
+// data != nullptr (nw_host_verify_batch_msgs_many): vote i's message is its own mlens[i] bytes
+// at data + moffs[i] in the place of the batch digest; nothing is read for a length of 0.
 int verify_batch_full(const uint8_t digest[32], const uint8_t* pks, const uint8_t* sigs,
-                      size_t n, const uint8_t* z16, uint64_t* fail_index) {
+                      size_t n, const uint8_t* z16, uint64_t* fail_index,
+                      const uint8_t* data = nullptr, const uint64_t* moffs = nullptr,
+                      const uint64_t* mlens = nullptr) {
   const Consts& C = consts();
   *fail_index = n;
   if (n == 0) return NW_OK;
@@ -527,7 +531,10 @@ int verify_batch_full(const uint8_t digest[32], const uint8_t* pks, const uint8_
     sc z, k, s, t;
     memset(z.w, 0, 32);
     memcpy(z.w, z16 + 16 * i, 16);
-    hram(k, sigs + 64 * i, pks + 32 * i, digest, 32);
+    if (data)
+      hram(k, sigs + 64 * i, pks + 32 * i, mlens[i] ? data + moffs[i] : data, (size_t)mlens[i]);
+    else
+      hram(k, sigs + 64 * i, pks + 32 * i, digest, 32);
     load_sc(s, sigs + 64 * i + 32);
     sc_mul(t, z, k);
     sc_recode(&dig[8 * i], z, 0x88888888u);
@@ -558,6 +565,17 @@ int verify_batch_full(const uint8_t digest[32], const uint8_t* pks, const uint8_
   return ge_is_identity(acc) ? NW_OK : NW_ERR_EQUATION;
 }
 }  // namespace
+
+int verify_batch_msgs(const uint8_t* data, const uint64_t* msg_offsets,
+                      const uint64_t* msg_lengths, const uint8_t* pks, const uint8_t* sigs,
+                      size_t n, const uint8_t* z16, uint64_t* fail_index) {
+  static const uint8_t none = 0;   // a call whose messages are all empty may pass no data
+  uint64_t fi = n;
+  const int st = verify_batch_full(nullptr, pks, sigs, n, z16, &fi, data ? data : &none,
+                                   msg_offsets, msg_lengths);
+  if (fail_index) *fail_index = fi;
+  return st;
+}
 
 int verify_batch(const uint8_t digest[32], const uint8_t* pks, const uint8_t* sigs, size_t n,
                  const uint8_t* z16, const Committee* com, uint64_t* fail_index) {
@@ -698,6 +716,29 @@ int nw_host_verify_batch_many(const uint8_t* digests, const uint8_t* pks, const 
     uint64_t fi = 0;
     const int st = nw::host::verify_batch(digests + 32 * b, pks + 32 * o, sigs + 64 * o, cnt,
                                           z16 ? z16 + 16 * o : nullptr, nullptr, &fi);
+    if (st < 0) return st;
+    status_out[b] = st;
+    if (fail_index_out) fail_index_out[b] = fi;
+  }
+  return 0;
+}
+
+int nw_host_verify_batch_msgs_many(const uint8_t* data, const uint64_t* msg_offsets,
+                                   const uint64_t* msg_lengths, const uint8_t* pks,
+                                   const uint8_t* sigs, const uint64_t* offsets, size_t nbatches,
+                                   const uint8_t* z16, int32_t* status_out,
+                                   uint64_t* fail_index_out) {
+  if (nbatches && (!offsets || !status_out)) return NW_E_INVALID_ARG;
+  const uint64_t nitems = nbatches ? offsets[nbatches] : 0;
+  if (nitems && (!msg_offsets || !msg_lengths || !pks || !sigs)) return NW_E_INVALID_ARG;
+  for (uint64_t i = 0; i < nitems; ++i)
+    if (msg_lengths[i] && !data) return NW_E_INVALID_ARG;
+  for (size_t b = 0; b < nbatches; ++b) {
+    const uint64_t o = offsets[b], cnt = offsets[b + 1] - o;
+    uint64_t fi = 0;
+    const int st = nw::host::verify_batch_msgs(data, msg_offsets + o, msg_lengths + o,
+                                               pks + 32 * o, sigs + 64 * o, cnt,
+                                               z16 ? z16 + 16 * o : nullptr, &fi);
     if (st < 0) return st;
     status_out[b] = st;
     if (fail_index_out) fail_index_out[b] = fi;

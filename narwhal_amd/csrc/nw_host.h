@@ -35,6 +35,12 @@ int verify_strict_msg(const uint8_t* msg, size_t len, const uint8_t pk[32],
 // OS CSPRNG. com (optional): votes whose key is a committee member take the keyed check.
 int verify_batch(const uint8_t digest[32], const uint8_t* pks, const uint8_t* sigs, size_t n,
                  const uint8_t* z16, const Committee* com, uint64_t* fail_index);
+// dalek's verify_batch(messages, signatures, public_keys): the same checks in the same order
+// with k_i = SHA-512(R_i || A_i || M_i) mod l, M_i = msg_lengths[i] bytes at data +
+// msg_offsets[i] (nothing is read for a length of 0; data may then be null).
+int verify_batch_msgs(const uint8_t* data, const uint64_t* msg_offsets,
+                      const uint64_t* msg_lengths, const uint8_t* pks, const uint8_t* sigs,
+                      size_t n, const uint8_t* z16, uint64_t* fail_index);
 // Header::verify / Vote::verify / Certificate::verify (primary/src/messages.rs:48-67,
 // 131-142, 189-215): NW_DAG_* status and index exactly as nw_certificates_verify_many.
 int header_verify(const Committee& c, const uint8_t* hb, size_t hlen, uint32_t np,

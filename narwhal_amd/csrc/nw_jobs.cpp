@@ -840,6 +840,122 @@ int submit_strict_msgs(int dev, const uint8_t* data, const uint64_t* offsets,
   return 0;
 }
 
+// verify_batch over per-vote messages of any length (msg_offsets / msg_lengths: one entry per
+// vote): the referenced bytes packed contiguously and the offsets rebased as submit_strict_msgs
+// does, the batches staged as submit_batch does. The k plane (32 bytes per vote) is the job's own
+// device memory, beside its batch workspace: no lease. The registered signers serve the call as
+// they serve submit_batch: the comb phase reads the plane, hashed before it. Never the fused
+// launches, so none of submit_batch's direct outputs, mapped inputs, gate or spin.
+int submit_batch_msgs(int dev, const uint8_t* data, const uint64_t* msg_offsets,
+                      const uint64_t* msg_lengths, const uint8_t* pks, const uint8_t* sigs,
+                      const uint64_t* offsets, size_t nbatches, const uint8_t* z16,
+                      int32_t* status_out, uint64_t* fail_index_out, nw_job** job) {
+  const size_t nitems = nbatches ? offsets[nbatches] : 0;
+  nw_job* j;
+  int rc = job_acquire(dev, &j);
+  if (rc) return rc;
+  if (nbatches == 0) {
+    *job = j;
+    return 0;
+  }
+  const size_t m = nitems ? nitems : 1;
+  const nw::ge_niels_pad* bcomb = nullptr;
+  bool signers = nitems != 0 && nw::rt::signers_registered(dev) &&
+                 nitems >= nw::batch_signers_min_votes();
+  if (signers) {   // as submit_batch: no memory for the B comb = without the path
+    const hipError_t eb = nw::bcomb_table(&bcomb);
+    if (eb == hipErrorOutOfMemory) {
+      (void)hipGetLastError();
+      signers = false;
+    } else if (eb != hipSuccess) {
+      return job_abort(j, set_err(NW_E_DEVICE, "keyed B comb build", eb));
+    }
+  }
+  uint64_t total = 0;
+  for (size_t i = 0; i < nitems; ++i) total += msg_lengths[i];
+  const size_t o_data = 0, o_mo = a256(total ? total : 1), o_ml = o_mo + a256(8 * m),
+               o_off = o_ml + a256(8 * m), o_pk = o_off + a256(8 * (nbatches + 1)),
+               o_sig = o_pk + a256(32 * m), o_z = o_sig + a256(64 * m),
+               o_st = o_z + (z16 ? a256(16 * m) : 0), o_fi = o_st + a256(4 * nbatches),
+               o_ct = o_fi + a256(8 * nbatches),   // the comb phase's six counters
+               o_ws = o_ct + (signers ? 256 : 0),
+               o_kp = o_ws + a256(nw::batch_workspace_bytes(nbatches, nitems)),
+               o_sg = o_kp + a256(32 * m),
+               end = o_sg + (signers ? a256(nw::batch_signers_bytes(nbatches, nitems)) : 0);
+  rc = job_reserve(j, o_ws, end);
+  if (rc) return job_abort(j, rc);
+  uint64_t* offs = reinterpret_cast<uint64_t*>(j->hbuf + o_mo);
+  uint64_t pos = 0;
+  for (size_t i = 0; i < nitems; ++i) {
+    offs[i] = pos;
+    pos += msg_lengths[i];
+  }
+  size_t i = 0;
+  while (i < nitems) {   // contiguous runs are copied in one go
+    size_t k = i + 1;
+    while (k < nitems && msg_offsets[k] == msg_offsets[k - 1] + msg_lengths[k - 1]) ++k;
+    const uint64_t bytes = offs[k - 1] + msg_lengths[k - 1] - offs[i];
+    if (bytes) memcpy(j->hbuf + o_data + offs[i], data + msg_offsets[i], bytes);
+    i = k;
+  }
+  memcpy(j->hbuf + o_off, offsets, 8 * (nbatches + 1));
+  if (nitems) {
+    memcpy(j->hbuf + o_ml, msg_lengths, 8 * nitems);
+    memcpy(j->hbuf + o_pk, pks, 32 * nitems);
+    memcpy(j->hbuf + o_sig, sigs, 64 * nitems);
+    if (z16) memcpy(j->hbuf + o_z, z16, 16 * nitems);
+  }
+  nw::z_key_t key;
+  rc = fill_key(key);
+  if (rc) return job_abort(j, rc);
+  rc = job_run(j, o_st, o_st, o_ws - o_st, [&]() -> int {
+    const uint32_t* const d_pk = reinterpret_cast<const uint32_t*>(j->dbuf + o_pk);
+    const uint32_t* const d_sig = reinterpret_cast<const uint32_t*>(j->dbuf + o_sig);
+    const uint64_t* const d_off = reinterpret_cast<const uint64_t*>(j->dbuf + o_off);
+    uint32_t* const kplane = reinterpret_cast<uint32_t*>(j->dbuf + o_kp);
+    JOB_HIP(nw::launch_strict_hram(reinterpret_cast<const uint8_t*>(j->dbuf + o_data),
+                                   reinterpret_cast<const uint64_t*>(j->dbuf + o_mo),
+                                   reinterpret_cast<const uint64_t*>(j->dbuf + o_ml), d_pk, d_sig,
+                                   nitems, kplane, j->stream),
+            "k_strict_hram launch (verify_batch over messages)");
+    const uint32_t* batch_ok = nullptr;
+    nw::batch_votes_t votes{};
+    const bool leave_out = signers && nw::batch_signers_votes();
+    if (signers) {
+      unsigned long long* const ctr = reinterpret_cast<unsigned long long*>(j->dbuf + o_ct);
+      nw::rt::SignersLease sl;
+      nw::strict_signers_t sg;
+      const int lrc = sl.acquire(dev, j->stream, &sg);
+      if (lrc < 0) return lrc;
+      if (lrc == 0) {
+        const hipError_t se = nw::launch_batch_signers(
+            kplane, d_off, nbatches, d_pk, d_sig, nitems, sg, bcomb, j->dbuf + o_sg, ctr,
+            &batch_ok, j->stream, leave_out ? &votes : nullptr, true);
+        const int rrc = sl.release();
+        JOB_HIP(se, "verify_batch launch over messages (registered signers)");
+        if (rrc) return rrc;
+      } else {
+        JOB_HIP(hipMemsetAsync(ctr, 0, 8 * kBstats, j->stream),
+                "hipMemsetAsync (signers' counters)");
+      }
+    }
+    JOB_HIP(nw::launch_verify_batch_msgs(
+                nullptr, nullptr, nullptr, d_off, offsets, nbatches, d_pk, d_sig, nitems,
+                z16 ? reinterpret_cast<const uint32_t*>(j->dbuf + o_z) : nullptr, key,
+                j->dbuf + o_ws, kplane, true, reinterpret_cast<int32_t*>(j->dbuf + o_st),
+                reinterpret_cast<uint64_t*>(j->dbuf + o_fi), j->stream, batch_ok,
+                batch_ok && votes.state ? &votes : nullptr),
+            "verify_batch launch over messages");
+    return 0;
+  });
+  if (rc) return job_abort(j, rc);
+  job_out(j, status_out, o_st, 4 * nbatches);
+  job_out(j, fail_index_out, o_fi, 8 * nbatches);
+  if (signers) j->bstats = reinterpret_cast<const uint64_t*>(j->hbuf + o_ct);
+  *job = j;
+  return 0;
+}
+
 // ---- primary messages ------------------------------------------------------------------
 // The sections of a job's staging buffers (pinned and device share one layout): nw_stage.hpp
 // states the committee's, the header stream's, the certificate votes' and the Vote messages';
@@ -1672,6 +1788,51 @@ int nw_submit_verify_batch_many(const uint8_t* digests, const uint8_t* pks, cons
   return submit_entry(job, check, one, many);
 }
 
+int nw_submit_verify_batch_msgs(const uint8_t* data, const uint64_t* msg_offsets,
+                                const uint64_t* msg_lengths, const uint8_t* pks,
+                                const uint8_t* sigs, const uint64_t* offsets, size_t nbatches,
+                                const uint8_t* z16, int32_t* status_out,
+                                uint64_t* fail_index_out, nw_job** job) {
+  const auto check = [&]() -> int {
+    if (nbatches && !offsets) return set_err(NW_E_INVALID_ARG, "null pointer");
+    if (nbatches) {
+      if (offsets[0] != 0) return set_err(NW_E_INVALID_ARG, "offsets[0] must be 0");
+      for (size_t b = 0; b < nbatches; ++b)
+        if (offsets[b + 1] < offsets[b]) return set_err(NW_E_INVALID_ARG, "offsets not monotone");
+    }
+    const size_t nitems = nbatches ? offsets[nbatches] : 0;
+    if (nitems && (!pks || !sigs || !msg_offsets || !msg_lengths))
+      return set_err(NW_E_INVALID_ARG, "null pointer");
+    for (size_t i = 0; i < nitems && !data; ++i)   // only empty messages need no data
+      if (msg_lengths[i]) return set_err(NW_E_INVALID_ARG, "null pointer");
+    return 0;
+  };
+  const auto one = [&](int dev) {
+    return submit_batch_msgs(dev, data, msg_offsets, msg_lengths, pks, sigs, offsets, nbatches,
+                             z16, status_out, fail_index_out, job);
+  };
+  const auto many = [&](const std::vector<int>& devs) {
+    // whole batches per part, about equal votes (+1 per batch for its fixed tail); each part's
+    // votes, message ranges and z16 start at its first vote (the ranges stay offsets into data)
+    std::vector<uint64_t> w(nbatches + 1);
+    for (size_t b = 0; b <= nbatches; ++b) w[b] = offsets[b] + b;
+    return fan_out(devs, weighted_bounds(nbatches, devs.size(), w),
+                   [&](int dev, size_t a, size_t e, nw_job** sub) {
+                     std::vector<uint64_t> off(e - a + 1);
+                     for (size_t b = a; b <= e; ++b) off[b - a] = offsets[b] - offsets[a];
+                     const uint64_t v0 = offsets[a];
+                     return submit_batch_msgs(
+                         dev, data, msg_offsets ? msg_offsets + v0 : nullptr,
+                         msg_lengths ? msg_lengths + v0 : nullptr, pks ? pks + 32 * v0 : nullptr,
+                         sigs ? sigs + 64 * v0 : nullptr, off.data(), e - a,
+                         z16 ? z16 + 16 * v0 : nullptr, status_out ? status_out + a : nullptr,
+                         fail_index_out ? fail_index_out + a : nullptr, sub);
+                   },
+                   job);
+  };
+  return submit_entry(job, check, one, many);
+}
+
 int nw_submit_sha512_digest32_many(const uint8_t* data, const uint64_t* offsets,
                                    const uint64_t* lengths, size_t n, uint8_t* out32,
                                    nw_job** job) {
@@ -2054,6 +2215,40 @@ int nw_verify_batch_many(const uint8_t* digests, const uint8_t* pks, const uint8
   return run_blocking(nw_submit_verify_batch_many(digests, pks, sigs, offsets, nbatches, z16,
                                                   status_out, nullptr, &j),
                       j);
+}
+
+int nw_verify_batch_msgs_many(const uint8_t* data, const uint64_t* msg_offsets,
+                              const uint64_t* msg_lengths, const uint8_t* pks,
+                              const uint8_t* sigs, const uint64_t* offsets, size_t nbatches,
+                              const uint8_t* z16, int32_t* status_out,
+                              uint64_t* fail_index_out) {
+  if (nbatches == 0) return nw::rt::ensure_init();
+  if (!status_out) return set_err(NW_E_INVALID_ARG, "null pointer");
+  nw_job* j = nullptr;
+  return run_blocking(nw_submit_verify_batch_msgs(data, msg_offsets, msg_lengths, pks, sigs,
+                                                  offsets, nbatches, z16, status_out,
+                                                  fail_index_out, &j),
+                      j);
+}
+
+int nw_signature_verify_batch_msgs(const uint8_t* data, const uint64_t* msg_offsets,
+                                   const uint64_t* msg_lengths, const uint8_t* pks,
+                                   const uint8_t* sigs, size_t n, const uint8_t* z16,
+                                   size_t* fail_index) {
+  if (n == 0) {   // no votes: Ok, as nw_signature_verify_batch
+    int rc = nw::rt::ensure_init();
+    if (rc) return rc;
+    if (fail_index) *fail_index = 0;
+    return NW_OK;
+  }
+  const uint64_t offs[2] = {0, n};
+  int32_t st = 0;
+  uint64_t fi = 0;
+  const int rc = nw_verify_batch_msgs_many(data, msg_offsets, msg_lengths, pks, sigs, offs, 1,
+                                           z16, &st, &fi);
+  if (rc) return rc;
+  if (fail_index) *fail_index = (size_t)fi;
+  return st;
 }
 
 int nw_certificates_verify_many(const nw_committee* committee, const nw_certificates* certs,

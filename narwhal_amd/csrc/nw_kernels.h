@@ -190,6 +190,13 @@ hipError_t launch_verify_strict_msgs(const uint8_t* data, const uint64_t* offset
                                      uint64_t* bitmap, const strict_ws_t& workspace,
                                      hipStream_t stream);
 
+// k_strict_hram alone, for the launchers of other translation units (launch_verify_batch_msgs,
+// launch_batch_signers' callers): k = SHA-512(R || A || M) mod l of items 0..n-1 into kplane + 8 i.
+// One lane per item; a wave runs as long as its longest message.
+hipError_t launch_strict_hram(const uint8_t* data, const uint64_t* offsets,
+                              const uint64_t* lengths, const uint32_t* pks, const uint32_t* sigs,
+                              uint64_t n, uint32_t* kplane, hipStream_t stream);
+
 hipError_t launch_keypair(const uint32_t* seeds, uint64_t n, uint32_t* pks, hipStream_t stream);
 
 hipError_t launch_sign(const uint32_t* sks, uint32_t sk_stride_words, const uint32_t* msgs,
@@ -327,6 +334,35 @@ hipError_t launch_verify_batch(const uint32_t* digests, const uint64_t* offsets,
                                uint32_t* done = nullptr, uint32_t done_seq = 0,
                                bool skip_pip = false,
                                const batch_votes_t* votes = nullptr);
+// verify_batch over per-vote messages of any length (dalek's verify_batch(messages, signatures,
+// public_keys)): vote i's message is msg_lengths[i] bytes at data + msg_offsets[i] (device
+// arrays, one entry per vote of the call, any alignment). k_strict_hram (launch_strict_hram) runs
+// once over all nitems votes of the call, before the slice loop, and writes k_i = SHA-512(R_i ||
+// A_i || M_i) mod l into kplane + 8 i; one lane per vote, a wave runs as long as its longest
+// message. Then launch_verify_batch's plan / expand / items / chunks / combine sequence and the
+// Pippenger kernels run with the instances that read k from the plane at the call-global vote
+// index (k_bv_items_k, k_bv_items_listed_k, k_pip_points_k) instead of hashing the batch digest.
+// kplane: 32 bytes per vote of memory the caller owns (a job's own device buffer, the nw_dev_*
+// caller's workspace): not a shared per-device buffer, so it needs no lease and two streams
+// cannot collide on it. hashed: the caller has already run launch_strict_hram on `stream` (the
+// comb phase reads the plane first). skip_group_ok / votes: launch_batch_signers' outputs, as
+// launch_verify_batch takes them with skip_per_group = 1 and skip_pip. Never the fused head (it
+// hashes the batch digest in the kernel and the input gate belongs to it) and, by choice, not the
+// fused tail either: a lone large batch runs k_pip_points_k, k_pip_sort and the separate tail
+// kernels, as a skip_pip call does; fuse_ctr, gate and done are refused (hipErrorInvalidValue).
+// Out of scope: k_bv_items_chunked (certificate callers only), the certificate groups, the keyed
+// (key_tables_t) path.
+hipError_t launch_verify_batch_msgs(const uint8_t* data, const uint64_t* msg_offsets,
+                                    const uint64_t* msg_lengths, const uint64_t* offsets,
+                                    const uint64_t* host_offsets, uint64_t nbatches,
+                                    const uint32_t* pks, const uint32_t* sigs, uint64_t nitems,
+                                    const uint32_t* z16, const z_key_t& zkey, void* workspace,
+                                    uint32_t* kplane, bool hashed, int32_t* status,
+                                    uint64_t* fail_index, hipStream_t stream,
+                                    const uint32_t* skip_group_ok = nullptr,
+                                    const batch_votes_t* votes = nullptr,
+                                    uint32_t* fuse_ctr = nullptr,
+                                    const input_gate_t* gate = nullptr, uint32_t* done = nullptr);
 // Signature::verify_batch under the registered signers (nw_kernels.hip, DESIGN.md 5 "Round 12"):
 // every vote of the call through the comb check under its registered key (sg.n != 0; bcomb: the
 // device's B comb), the parities in batched inversions; *batch_ok_out (in scratch, nbatches words)
@@ -342,6 +378,8 @@ hipError_t launch_verify_batch(const uint32_t* digests, const uint64_t* offsets,
 // batch_signers_votes()): no list, every vote of a batch sent on runs, counter 4 stays 0.
 // batch_signers_min_votes(): the call size from which the path is taken (NW_BATCH_SIGNERS_MIN_VOTES,
 // default 1; NW_BATCH_SIGNERS=0: never), read per call.
+// kplane: `digests` is the call's k plane (launch_strict_hram), one row per vote, and the comb
+// check reads vote i's k from row i (k_batch_signers_k) instead of hashing its batch's digest.
 constexpr int kBatchSignersCounters = 6;
 size_t batch_signers_bytes(uint64_t nbatches, uint64_t nitems);
 uint64_t batch_signers_min_votes();
@@ -351,7 +389,7 @@ hipError_t launch_batch_signers(const uint32_t* digests, const uint64_t* offsets
                                 const strict_signers_t& sg, const struct ge_niels_pad* bcomb,
                                 void* scratch, unsigned long long* counters,
                                 const uint32_t** batch_ok_out, hipStream_t stream,
-                                batch_votes_t* votes_out = nullptr);
+                                batch_votes_t* votes_out = nullptr, bool kplane = false);
 
 // Certificate::verify vote batches merged over groups of certificates (nw_batch.hip):
 // cert_group_size() = certificates per group, 0 when the merge does not apply;

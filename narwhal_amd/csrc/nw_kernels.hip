@@ -24,6 +24,7 @@
 #include <algorithm>
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 namespace nw {
@@ -1310,16 +1311,20 @@ __global__ __launch_bounds__(256) void k_batch_signers_init(uint64_t nbatches,
   if (b < kBsCounters) ctr[b] = 0ull;
   if (b == 0 && nlist) *nlist = 0u;
 }
-__global__ __launch_bounds__(256, NW_COMB_WAVES) void k_batch_signers(
+// Src = strict_src_global: k from the digest of the vote's batch; strict_src_plane
+// (k_batch_signers_k, the per-message entries): k from row i of the call's k plane.
+template <class Src>
+__device__ __forceinline__ void batch_signers_lane(
     const uint32_t* __restrict__ digests, const uint64_t* __restrict__ offsets, uint64_t nbatches,
     const uint32_t* __restrict__ pks, const uint32_t* __restrict__ sigs, uint64_t nv,
-    signers_view sv, const uint32_t* __restrict__ rok, const uint32_t* __restrict__ rlam,
+    const signers_view& sv, const uint32_t* __restrict__ rok, const uint32_t* __restrict__ rlam,
     const ge_niels_pad* __restrict__ rtabs, const ge_niels_pad* __restrict__ bcomb,
-    uint32_t* __restrict__ batch_ok, vote_planes_t vp) {
+    uint32_t* __restrict__ batch_ok, const vote_planes_t& vp) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nv) return;
   const uint64_t b = vote_batch(offsets, nbatches, i);
-  const strict_src_global src{pks + 8 * i, sigs + 16 * i, digests + 8 * b};
+  constexpr bool kPlane = std::is_same<Src, strict_src_plane>::value;
+  const Src src{pks + 8 * i, sigs + 16 * i, digests + 8 * (kPlane ? i : b)};
   const keyspec ks = keyspec_for(8);
   fe X, Z;
   const uint32_t st = batch_signers_vote(
@@ -1334,6 +1339,24 @@ __global__ __launch_bounds__(256, NW_COMB_WAVES) void k_batch_signers(
   }
   if (st == kVoteFail) batch_ok[b] = 0u;
   vp.state[i] = st;
+}
+__global__ __launch_bounds__(256, NW_COMB_WAVES) void k_batch_signers(
+    const uint32_t* __restrict__ digests, const uint64_t* __restrict__ offsets, uint64_t nbatches,
+    const uint32_t* __restrict__ pks, const uint32_t* __restrict__ sigs, uint64_t nv,
+    signers_view sv, const uint32_t* __restrict__ rok, const uint32_t* __restrict__ rlam,
+    const ge_niels_pad* __restrict__ rtabs, const ge_niels_pad* __restrict__ bcomb,
+    uint32_t* __restrict__ batch_ok, vote_planes_t vp) {
+  batch_signers_lane<strict_src_global>(digests, offsets, nbatches, pks, sigs, nv, sv, rok, rlam,
+                                        rtabs, bcomb, batch_ok, vp);
+}
+__global__ __launch_bounds__(256, NW_COMB_WAVES) void k_batch_signers_k(
+    const uint32_t* __restrict__ kplane, const uint64_t* __restrict__ offsets, uint64_t nbatches,
+    const uint32_t* __restrict__ pks, const uint32_t* __restrict__ sigs, uint64_t nv,
+    signers_view sv, const uint32_t* __restrict__ rok, const uint32_t* __restrict__ rlam,
+    const ge_niels_pad* __restrict__ rtabs, const ge_niels_pad* __restrict__ bcomb,
+    uint32_t* __restrict__ batch_ok, vote_planes_t vp) {
+  batch_signers_lane<strict_src_plane>(kplane, offsets, nbatches, pks, sigs, nv, sv, rok, rlam,
+                                       rtabs, bcomb, batch_ok, vp);
 }
 __global__ __launch_bounds__(256) void k_batch_signers_inv(const uint64_t* __restrict__ offsets,
                                                            uint64_t nbatches, uint64_t nv,
@@ -2179,6 +2202,16 @@ hipError_t launch_verify_strict(const uint32_t* msgs, uint32_t msg_stride_words,
                                              : launch_strict_keyed_fast(in, ws.base, kt, btw, bcomb);
 }
 
+hipError_t launch_strict_hram(const uint8_t* data, const uint64_t* offsets,
+                              const uint64_t* lengths, const uint32_t* pks, const uint32_t* sigs,
+                              uint64_t n, uint32_t* kplane, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  if (!kplane || !offsets || !lengths) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_strict_hram, dim3(grid_for(n, 256)), dim3(256), 0, stream, data, offsets,
+                     lengths, pks, sigs, n, kplane);
+  return hipGetLastError();
+}
+
 // The strict launch over messages of any length: k of every item into the plane, then the
 // two-pass launch (always: NW_STRICT_TRIAGE=0 is an A/B hook of the 32-byte launch) with the
 // plane in the place of the digests.
@@ -2279,7 +2312,7 @@ hipError_t launch_batch_signers(const uint32_t* digests, const uint64_t* offsets
                                 const strict_signers_t& sg, const ge_niels_pad* bcomb,
                                 void* scratch, unsigned long long* counters,
                                 const uint32_t** batch_ok_out, hipStream_t stream,
-                                batch_votes_t* votes_out) {
+                                batch_votes_t* votes_out, bool kplane) {
   if (nbatches == 0 || sg.n == 0 || !sg.lam || !bcomb) return hipErrorInvalidValue;
   if (nitems > 0xffffffffull) votes_out = nullptr;   // the list's entries are 32 bits
   uint32_t* const base = static_cast<uint32_t*>(scratch);
@@ -2290,6 +2323,12 @@ hipError_t launch_batch_signers(const uint32_t* digests, const uint64_t* offsets
   hipLaunchKernelGGL(k_batch_signers_init, dim3(grid_for(nbatches, 256)), dim3(256), 0, stream,
                      nbatches, batch_ok, counters, votes_out ? nlist : nullptr);
   if (nitems) {
+    if (kplane)
+      hipLaunchKernelGGL(k_batch_signers_k, dim3(grid_for(nitems, 256)), dim3(256), 0, stream,
+                         digests, offsets, nbatches, pks, sigs, nitems,
+                         signers_view{sg.keys, sg.slots, sg.cap}, sg.ok, sg.lam, sg.tabs, bcomb,
+                         batch_ok, vp);
+    else
     hipLaunchKernelGGL(k_batch_signers, dim3(grid_for(nitems, 256)), dim3(256), 0, stream, digests,
                        offsets, nbatches, pks, sigs, nitems, signers_view{sg.keys, sg.slots, sg.cap},
                        sg.ok, sg.lam, sg.tabs, bcomb, batch_ok, vp);
