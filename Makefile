@@ -1,6 +1,6 @@
 # Builds the MI355X engine (narwhal_amd/libnarwhal_amd.so, gfx950 only), the CPU oracle
 # (test infrastructure) and the host check libraries of the kernels' arithmetic, of the wire
-# decoder and of the message jobs' staging layout, and the gfx950 harness of the arithmetic on
+# decoder, of the message jobs' staging layout and of a verify_batch call, and the gfx950 harness of the arithmetic on
 # raw limbs (test infrastructure).
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
@@ -10,7 +10,7 @@ HDRS := $(wildcard $(CSRC)/*.hpp) $(CSRC)/nw_kernels.h $(CSRC)/nw_runtime.h $(CS
 LIB := narwhal_amd/libnarwhal_amd.so
 BUILD := build
 
-all: $(LIB) oracle hostcheck lpcheck wirecheck stagecheck loadgen
+all: $(LIB) oracle hostcheck lpcheck wirecheck stagecheck batchcheck loadgen
 
 $(BUILD)/nw_kernels.o: $(CSRC)/nw_kernels.hip $(HDRS)
 	@mkdir -p $(BUILD)
@@ -91,6 +91,18 @@ stagesan: tools/stage_san
 tools/stage_san: tools/stagecheck.hip $(CSRC)/nw_stage.hpp include/narwhal_amd.h
 	g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -DSTAGECHECK_MAIN -Iinclude -x c++ $< -o $@
 
+# a verify_batch call's refusal rules (nw_batch_call.hpp), the batch job's section plan and the
+# packing of per-item messages (nw_stage.hpp) for the CPU (tests/test_batch_call_cpu.py), and the
+# same file with its main under AddressSanitizer / UBSan (not part of `all`):
+# make batchsan && tools/batch_san
+batchcheck: tools/libnw_batchcheck.so
+BATCHCHECK_DEPS := tools/batchcheck.hip $(CSRC)/nw_batch_call.hpp $(CSRC)/nw_stage.hpp include/narwhal_amd.h
+tools/libnw_batchcheck.so: $(BATCHCHECK_DEPS)
+	$(HIPCC) --cuda-host-only -O2 -std=c++17 -fPIC -shared -Iinclude $< -o $@
+batchsan: tools/batch_san
+tools/batch_san: $(BATCHCHECK_DEPS)
+	$(HIPCC) --cuda-host-only -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -DBATCHCHECK_MAIN -Iinclude $< -o $@
+
 # the key set's sizing, region planning and probe / build / triage / ladder sequence, and the
 # registered signers' hash table and one slice through it (nw_kernels.h, nw_strict.hpp;
 # tools/hostcheck.hip's main) under AddressSanitizer / UBSan, as a stand-alone CPU program
@@ -126,7 +138,7 @@ tools/ubench_valu: tools/ubench_valu.hip
 	$(HIPCC) --offload-arch=$(ARCH) -O3 $< -o $@
 
 clean:
-	rm -rf $(BUILD) $(LIB) tools/libnw_hostcheck.so tools/libnw_lpcheck.so tools/libnw_wirecheck.so tools/libnw_stagecheck.so tools/libnw_loadgen.so tools/service_stress tools/service_stress_tsan tools/wire_canon_san tools/stage_san tools/keyset_san tools/hram_lane_san
+	rm -rf $(BUILD) $(LIB) tools/libnw_hostcheck.so tools/libnw_lpcheck.so tools/libnw_wirecheck.so tools/libnw_stagecheck.so tools/libnw_batchcheck.so tools/libnw_loadgen.so tools/service_stress tools/service_stress_tsan tools/wire_canon_san tools/stage_san tools/batch_san tools/keyset_san tools/hram_lane_san
 	$(MAKE) -s -C oracle clean
 
-.PHONY: all oracle hostcheck lpcheck wirecheck stagecheck wiresan stagesan keysetsan hramsan loadgen stress ubench clean
+.PHONY: all oracle hostcheck lpcheck wirecheck stagecheck batchcheck batchsan wiresan stagesan keysetsan hramsan loadgen stress ubench clean

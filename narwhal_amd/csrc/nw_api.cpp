@@ -530,33 +530,54 @@ static int host_offsets_of(const uint64_t* dev_offsets, const uint64_t* host_off
   return 0;
 }
 
+// The prologue of the two device entries: the context, the null checks (null_arg: the entry's
+// own), the coefficient key, the stream, the host offsets and their range, and every field of the
+// call but `digests`. call.nbatches stays 0 for a call without batches: nothing to launch.
+struct DevBatch {
+  hipStream_t s = nullptr;
+  nw::z_key_t key;
+  std::vector<uint64_t> tmp;
+  nw::batch_call_t call;
+};
+static int dev_batch_begin(bool null_arg, const void* pks, const void* sigs,
+                           const uint64_t* offsets, const uint64_t* host_offsets, size_t nbatches,
+                           size_t nitems, const void* z16, const uint8_t* zkey32, void* workspace,
+                           int32_t* status_out, uint64_t* fail_index, void* stream, DevBatch* d) {
+  DevCtx* c;
+  int rc = begin(&c);
+  if (rc || nbatches == 0) return rc;
+  if (null_arg || !offsets || !workspace || !status_out || (nitems && (!pks || !sigs)))
+    return set_err(NW_E_INVALID_ARG, "null pointer");
+  rc = fill_key(d->key, zkey32);
+  if (rc) return rc;
+  d->s = pick_stream(stream, c);
+  const uint64_t* ho;
+  rc = host_offsets_of(offsets, host_offsets, nbatches, d->s, d->tmp, &ho);
+  if (rc) return rc;
+  if (ho[0] != 0 || ho[nbatches] != nitems)
+    return set_err(NW_E_INVALID_ARG, "offsets must run from 0 to nitems");
+  nw::batch_call_t& k = d->call;
+  k.offsets = offsets, k.host_offsets = ho;
+  k.nbatches = nbatches;
+  k.pks = static_cast<const uint32_t*>(pks), k.sigs = static_cast<const uint32_t*>(sigs);
+  k.nitems = nitems;
+  k.z16 = static_cast<const uint32_t*>(z16);
+  k.zkey = &d->key;
+  k.status = status_out, k.fail_index = fail_index, k.workspace = workspace;
+  return 0;
+}
+
 int nw_dev_verify_batch_many(const void* digests, const void* pks, const void* sigs,
                              const uint64_t* offsets, const uint64_t* host_offsets,
                              size_t nbatches, size_t nitems, const void* z16,
                              const uint8_t* zkey32, void* workspace, int32_t* status_out,
                              uint64_t* fail_index, void* stream) {
-  DevCtx* c;
-  int rc = begin(&c);
-  if (rc) return rc;
-  if (nbatches == 0) return 0;
-  if (!digests || !offsets || !workspace || !status_out || (nitems && (!pks || !sigs)))
-    return set_err(NW_E_INVALID_ARG, "null pointer");
-  nw::z_key_t key;
-  rc = fill_key(key, zkey32);
-  if (rc) return rc;
-  hipStream_t s = pick_stream(stream, c);
-  std::vector<uint64_t> tmp;
-  const uint64_t* ho;
-  rc = host_offsets_of(offsets, host_offsets, nbatches, s, tmp, &ho);
-  if (rc) return rc;
-  if (ho[0] != 0 || ho[nbatches] != nitems)
-    return set_err(NW_E_INVALID_ARG, "offsets must run from 0 to nitems");
-  NW_HIP(nw::launch_verify_batch(static_cast<const uint32_t*>(digests), offsets, ho, nbatches,
-                                 static_cast<const uint32_t*>(pks),
-                                 static_cast<const uint32_t*>(sigs), nitems,
-                                 static_cast<const uint32_t*>(z16), key, workspace, status_out,
-                                 fail_index, s),
-         "verify_batch launch");
+  DevBatch d;
+  const int rc = dev_batch_begin(!digests, pks, sigs, offsets, host_offsets, nbatches, nitems, z16,
+                                 zkey32, workspace, status_out, fail_index, stream, &d);
+  if (rc || d.call.nbatches == 0) return rc;
+  d.call.digests = static_cast<const uint32_t*>(digests);
+  NW_HIP(nw::launch_verify_batch(d.call, d.s), "verify_batch launch");
   return 0;
 }
 
@@ -575,31 +596,16 @@ int nw_dev_verify_batch_msgs_many(const void* data, const uint64_t* msg_offsets,
                                   size_t nbatches, size_t nitems, const void* z16,
                                   const uint8_t* zkey32, void* workspace, int32_t* status_out,
                                   uint64_t* fail_index, void* stream) {
-  DevCtx* c;
-  int rc = begin(&c);
-  if (rc) return rc;
-  if (nbatches == 0) return 0;
   // data may be null when every message is empty: nothing is read through it then
-  if (!offsets || !workspace || !status_out ||
-      (nitems && (!msg_offsets || !msg_lengths || !pks || !sigs)))
-    return set_err(NW_E_INVALID_ARG, "null pointer");
-  nw::z_key_t key;
-  rc = fill_key(key, zkey32);
-  if (rc) return rc;
-  hipStream_t s = pick_stream(stream, c);
-  std::vector<uint64_t> tmp;
-  const uint64_t* ho;
-  rc = host_offsets_of(offsets, host_offsets, nbatches, s, tmp, &ho);
-  if (rc) return rc;
-  if (ho[0] != 0 || ho[nbatches] != nitems)
-    return set_err(NW_E_INVALID_ARG, "offsets must run from 0 to nitems");
-  uint32_t* const kplane = reinterpret_cast<uint32_t*>(
+  DevBatch d;
+  const int rc = dev_batch_begin(nitems && (!msg_offsets || !msg_lengths), pks, sigs, offsets,
+                                 host_offsets, nbatches, nitems, z16, zkey32, workspace,
+                                 status_out, fail_index, stream, &d);
+  if (rc || d.call.nbatches == 0) return rc;
+  d.call.digests = reinterpret_cast<const uint32_t*>(
       static_cast<char*>(workspace) + batch_msgs_plane_offset(nbatches, nitems));
-  NW_HIP(nw::launch_verify_batch_msgs(static_cast<const uint8_t*>(data), msg_offsets, msg_lengths,
-                                      offsets, ho, nbatches, static_cast<const uint32_t*>(pks),
-                                      static_cast<const uint32_t*>(sigs), nitems,
-                                      static_cast<const uint32_t*>(z16), key, workspace, kplane,
-                                      false, status_out, fail_index, s),
+  NW_HIP(nw::launch_verify_batch_msgs(d.call, static_cast<const uint8_t*>(data), msg_offsets,
+                                      msg_lengths, false, d.s),
          "verify_batch launch over messages");
   return 0;
 }
@@ -934,14 +940,22 @@ int cert_pipeline(int dev, const nw_committee& com, const nw_certificates& cs,
                                      (uint32_t)com.nauth, K, p_cert, w.batch_st, w.batch_idx,
                                      &group_ok, s),
              "small certificate groups (votes)");
-    else
-      NW_HIP(nw::launch_verify_batch(w.cert_digest, cs.vote_offsets, host_vote_offsets, n,
-                                     reinterpret_cast<const uint32_t*>(cs.vote_pks),
-                                     reinterpret_cast<const uint32_t*>(cs.vote_sigs), cs.nvotes,
-                                     static_cast<const uint32_t*>(z16), key, w.batch_ws,
-                                     w.batch_st, w.batch_idx, s, use_keys ? &kt : nullptr,
-                                     group_ok, K, keyed ? std::max(p_cert, 1e-3) : 1.0),
-             "verify_batch (votes)");
+    else {
+      nw::batch_call_t vb;
+      vb.digests = w.cert_digest;
+      vb.offsets = cs.vote_offsets, vb.host_offsets = host_vote_offsets;
+      vb.nbatches = n;
+      vb.pks = reinterpret_cast<const uint32_t*>(cs.vote_pks);
+      vb.sigs = reinterpret_cast<const uint32_t*>(cs.vote_sigs);
+      vb.nitems = cs.nvotes;
+      vb.z16 = static_cast<const uint32_t*>(z16);
+      vb.zkey = &key;
+      vb.status = w.batch_st, vb.fail_index = w.batch_idx, vb.workspace = w.batch_ws;
+      vb.keys = use_keys ? &kt : nullptr;
+      vb.skip_group_ok = group_ok, vb.skip_per_group = K;
+      vb.active_frac = keyed ? std::max(p_cert, 1e-3) : 1.0;
+      NW_HIP(nw::launch_verify_batch(vb, s), "verify_batch (votes)");
+    }
     if (fb_dev)
       NW_HIP(nw::launch_group_feedback(group_ok, n, K,
                                        ((keyed ? 2u : small ? 1u : 0u) << 24) | (uint32_t)K,

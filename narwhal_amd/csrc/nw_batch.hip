@@ -2533,20 +2533,27 @@ __global__ __launch_bounds__(256) void k_pip_points_sorted(
 // that size, the list holds *pip_count of them, and the fused launches are never taken: they
 // order themselves by tickets and counters, and a block that left early would leave another
 // waiting.
-hipError_t launch_pip(const uint32_t* digests, const uint64_t* offsets, uint64_t b, uint64_t e,
-                uint64_t i0, uint64_t i1, uint32_t pmin, uint64_t npip, uint64_t pmax,
-                const uint32_t* pks, const uint32_t* sigs, const uint32_t* z16,
-                const z_key_t& zkey, const bv_ws& w, int32_t* status, uint64_t* fail_index,
-                const pip_group_t& grp, hipStream_t stream,
-                uint32_t* fctr, const input_gate_t* gate = nullptr, uint32_t* done = nullptr,
-                uint32_t done_seq = 0, const batch_skip_t& sk = batch_skip_t{nullptr, 1},
-                const uint32_t* pip_count = nullptr, const uint32_t* vstate = nullptr,
-                bool kplane = false) {
+struct pip_slice_t {
+  uint64_t b, e, i0, i1;   // the slice's batches (or groups) and votes
+  uint32_t pmin;
+  uint64_t npip, pmax;
+  uint32_t* fctr;              // the fused launches' zeroed counters
+  const uint32_t* pip_count;   // skip_pip: the plan's device-side count (else null)
+};
+hipError_t launch_pip(const batch_call_t& c, const pip_slice_t& s, const bv_ws& w,
+                      const pip_group_t& grp, hipStream_t stream) {
+  const auto [b, e, i0, i1, pmin, npip, pmax, fctr, pip_count] = s;
+  const uint32_t *const digests = c.digests, *const pks = c.pks, *const sigs = c.sigs,
+                 *const z16 = c.z16, *const vstate = c.votes ? c.votes->state : nullptr;
+  const uint64_t* const offsets = c.offsets;
+  const z_key_t& zkey = *c.zkey;
+  const batch_skip_t sk{c.skip_group_ok, c.skip_per_group ? c.skip_per_group : 1};
+  const bool kplane = c.kplane;
   const bool group = grp.cert_vote_offsets != nullptr;
   // over the k plane (`digests` is the plane): plain batches, and never the fused launches
   // (k_pip_points_sorted hashes the batch digest itself and the input gate belongs to it; the
   // fused tail is not taken behind the unfused head either, it stays the digest entry's)
-  if (kplane && (group || gate || done)) return hipErrorInvalidValue;
+  if (kplane && (group || c.gate || c.done)) return hipErrorInvalidValue;
   const uint32_t extra = group ? grp.nkeys : 0;   // key sums
   const uint32_t roles = group ? 2 : 3;
   const uint64_t wv = (i1 - i0 + 63) / 64;   // waves per role
@@ -2564,7 +2571,7 @@ hipError_t launch_pip(const uint32_t* digests, const uint64_t* offsets, uint64_t
     hipLaunchKernelGGL(k_pip_points_sorted, dim3(npb + kPipWin * ks), dim3(256), lds, stream,
                        digests, offsets, b, i0, i1, pks, sigs, z16, zkey, w.items, w.tabs, npb,
                        (uint32_t)wv, ks, fctr, head_stamps(npb + kPipWin * ks),
-                       gate ? *gate : input_gate_t{nullptr, 0u, 64u});
+                       c.gate ? *c.gate : input_gate_t{nullptr, 0u, 64u});
   } else {
     const dim3 gp((unsigned)((wv * roles * 64 + 255) / 256));
     if (kplane && vstate)
@@ -2606,8 +2613,8 @@ hipError_t launch_pip(const uint32_t* digests, const uint64_t* offsets, uint64_t
     static const uint32_t lds = (uint32_t)env_u64_zero("NW_PIP_FUSE_LDS", kFuseLds);   // A/B
     const uint32_t nblk = nbk + 2 + kFuseTopParts + (kPipWin - 1) * kFuseParts;
     hipLaunchKernelGGL(k_pip_tail_fused, dim3(nblk), dim3(256), lds, stream, offsets, b, i0, lg,
-                       nbk, w.tabs, fctr, status, fail_index, fuse_stamps(nblk), w.items,
-                       fuse_head ? 1 : 0, done, done_seq);
+                       nbk, w.tabs, fctr, c.status, c.fail_index, fuse_stamps(nblk), w.items,
+                       fuse_head ? 1 : 0, c.done, c.done_seq);
     return hipGetLastError();
   }
   const int xcd = npip >= 8;
@@ -2624,7 +2631,7 @@ hipError_t launch_pip(const uint32_t* digests, const uint64_t* offsets, uint64_t
     hipLaunchKernelGGL(k_pip_windows, dim3(kPipWin + 1, (unsigned)npip), dim3(64), 0, stream,
                        w.pip_list, offsets, b, i0, extra, pmin, w.tabs, pip_count);
   hipLaunchKernelGGL(k_pip_final, dim3((unsigned)npip), dim3(64), 0, stream, w.pip_list,
-                     offsets, b, i0, w.tabs, status, fail_index, extra, pmin, grp.group_ok,
+                     offsets, b, i0, w.tabs, c.status, c.fail_index, extra, pmin, grp.group_ok,
                      pip_count);
   return hipGetLastError();
 }
@@ -2657,41 +2664,27 @@ __global__ __launch_bounds__(256) void k_grp_setup(const uint64_t* __restrict__ 
   }
 }
 
-// launch_verify_batch's sequence. kplane (launch_verify_batch_msgs): `digests` is the call's k
-// plane, 8 words per vote, and the item and point kernels are their plane instances; plain
-// batches only (no key tables, no certificate skip list's compacted items), never the fused
-// launches.
-hipError_t verify_batch_run(const uint32_t* digests, const uint64_t* offsets,
-                            const uint64_t* host_offsets, uint64_t nbatches,
-                            const uint32_t* pks, const uint32_t* sigs, uint64_t nitems,
-                            const uint32_t* z16, const z_key_t& zkey, void* workspace,
-                            int32_t* status, uint64_t* fail_index, hipStream_t stream,
-                            const key_tables_t* keys, const uint32_t* skip_group_ok,
-                            uint64_t skip_per_group, double active_frac,
-                            uint32_t* fuse_ctr, const input_gate_t* gate,
-                            uint32_t* done, uint32_t done_seq, bool skip_pip,
-                            const batch_votes_t* votes, bool kplane) {
-  if (kplane && (keys || fuse_ctr || gate || done || active_frac < 1.0 ||
-                 (skip_group_ok && !skip_pip)))
-    return hipErrorInvalidValue;
-  // Pippenger batches under a skip list take the separate kernels only (launch_pip)
-  if (skip_pip && (!skip_group_ok || fuse_ctr || gate || done)) return hipErrorInvalidValue;
-  // the comb phase's vote list: its callers' plain batches only (a vote's state says nothing
-  // about a keyed item, and the list's indices are 32 bits)
-  if (votes && (!skip_pip || skip_per_group != 1 || keys || active_frac < 1.0 ||
-                nitems > 0xffffffffull))
-    return hipErrorInvalidValue;
-  // a gate is honoured by the fused head only: refuse it anywhere else (its waves would
-  // read bytes the CPU has not written yet)
-  if (gate && !verify_batch_gate_ok(nbatches, nitems)) return hipErrorInvalidValue;
-  if (gate && (gate->chunk == 0 || gate->chunk % 64 != 0)) return hipErrorInvalidValue;
-  if (done && !verify_batch_outputs_direct(nbatches, nitems)) return hipErrorInvalidValue;
-  const key_tables_t kt = keys ? *keys : key_tables_t{nullptr, nullptr, nullptr, {}};
-  const batch_skip_t sk{skip_group_ok, skip_per_group ? skip_per_group : 1};
+// launch_verify_batch's sequence (the call: nw_batch_call.hpp).
+hipError_t verify_batch_run(const batch_call_t& c, hipStream_t stream) {
+  const uint64_t nbatches = c.nbatches, nitems = c.nitems;
+  const hipError_t ce = batch_call_check(c, verify_batch_gate_ok(nbatches, nitems),
+                                         verify_batch_outputs_direct(nbatches, nitems));
+  if (ce != hipSuccess) return ce;
+  const uint32_t* const digests = c.digests;
+  const uint64_t *const offsets = c.offsets, *const host_offsets = c.host_offsets;
+  const uint32_t *const pks = c.pks, *const sigs = c.sigs, *const z16 = c.z16;
+  const z_key_t& zkey = *c.zkey;
+  int32_t* const status = c.status;
+  uint64_t* const fail_index = c.fail_index;
+  const uint32_t* const skip_group_ok = c.skip_group_ok;
+  const bool skip_pip = c.skip_pip, kplane = c.kplane;
+  const batch_votes_t* const votes = c.votes;
+  const key_tables_t kt = c.keys ? *c.keys : key_tables_t{nullptr, nullptr, nullptr, {}};
+  const batch_skip_t sk{skip_group_ok, c.skip_per_group ? c.skip_per_group : 1};
   if (nbatches == 0) return hipSuccess;
   const uint64_t cap = std::min<uint64_t>(nitems + nbatches, slice_units());
   bv_ws w;
-  bv_layout(cap, static_cast<char*>(workspace), &w);
+  bv_layout(cap, static_cast<char*>(c.workspace), &w);
   // Chunk size: fill the chip (~2 waves per SIMD of chunk lanes) but share the 252
   // doublings over as many votes as possible.
   // With a skip list only a fraction active_frac of the votes runs (the caller's estimate):
@@ -2701,7 +2694,7 @@ hipError_t verify_batch_run(const uint32_t* digests, const uint64_t* offsets,
   // 128-doubling ladder (config 2 at 1 % invalid, N = 10 / 50 / 100: 0.82 / 0.79 / 0.80 of
   // the all-valid rate with chunks of >= 4 votes, 0.88 / 0.88 / 0.87 with 1).
   const uint64_t target_lanes = 256ull * 4 * 2 * 64;
-  const double frac = skip_group_ok ? std::min(1.0, std::max(1e-6, active_frac)) : 1.0;
+  const double frac = skip_group_ok ? std::min(1.0, std::max(1e-6, c.active_frac)) : 1.0;
   const uint64_t run_votes = (uint64_t)(frac * (double)std::min(nitems, cap));
   uint32_t C = (uint32_t)std::min<uint64_t>(
       kMaxChunk, std::max<uint64_t>(1, run_votes / target_lanes));
@@ -2736,7 +2729,7 @@ hipError_t verify_batch_run(const uint32_t* digests, const uint64_t* offsets,
     const uint64_t i0 = host_offsets[b], i1 = host_offsets[e];
     const unsigned nblk = (unsigned)((e - b + 1023) / 1024);
     // the caller's zeroed counters (fused path only, verify_batch_outputs_direct)
-    const bool own_ctr = fuse_ctr && nbatches == 1 && pip_fuse_head_on() &&
+    const bool own_ctr = c.fuse_ctr && nbatches == 1 && pip_fuse_head_on() &&
                          verify_batch_outputs_direct(nbatches, nitems);
     const uint32_t* const pip_count = skip_pip ? w.plan_tot + 3 * nblk + 2 : nullptr;
     if (npip == e - b && own_ctr) {
@@ -2790,11 +2783,9 @@ hipError_t verify_batch_run(const uint32_t* digests, const uint64_t* offsets,
                          stream, digests, offsets, b, e, i0, i1, pmin, pks, sigs, z16, zkey,
                          w.items, w.tabs, kt, sk);
     if (npip) {
-      const hipError_t pe = launch_pip(digests, offsets, b, e, i0, i1, pmin, npip, pmax, pks,
-                                       sigs, z16, zkey, w, status, fail_index, nogrp, stream,
-                                       own_ctr ? fuse_ctr : w.chunk_start, gate, done,
-                                       done_seq, sk, pip_count,
-                                       votes ? votes->state : nullptr, kplane);
+      const pip_slice_t ps{b, e, i0, i1, pmin, npip, pmax, own_ctr ? c.fuse_ctr : w.chunk_start,
+                           pip_count};
+      const hipError_t pe = launch_pip(c, ps, w, nogrp, stream);
       if (pe != hipSuccess) return pe;
     }
     if (chunks && votes)
@@ -2821,44 +2812,22 @@ hipError_t verify_batch_run(const uint32_t* digests, const uint64_t* offsets,
 
 }  // namespace
 
-hipError_t launch_verify_batch(const uint32_t* digests, const uint64_t* offsets,
-                               const uint64_t* host_offsets, uint64_t nbatches,
-                               const uint32_t* pks, const uint32_t* sigs, uint64_t nitems,
-                               const uint32_t* z16, const z_key_t& zkey, void* workspace,
-                               int32_t* status, uint64_t* fail_index, hipStream_t stream,
-                               const key_tables_t* keys, const uint32_t* skip_group_ok,
-                               uint64_t skip_per_group, double active_frac,
-                               uint32_t* fuse_ctr, const input_gate_t* gate,
-                               uint32_t* done, uint32_t done_seq, bool skip_pip,
-                               const batch_votes_t* votes) {
-  return verify_batch_run(digests, offsets, host_offsets, nbatches, pks, sigs, nitems, z16, zkey,
-                          workspace, status, fail_index, stream, keys, skip_group_ok,
-                          skip_per_group, active_frac, fuse_ctr, gate, done, done_seq, skip_pip,
-                          votes, false);
+hipError_t launch_verify_batch(const batch_call_t& call, hipStream_t stream) {
+  return verify_batch_run(call, stream);
 }
 
-hipError_t launch_verify_batch_msgs(const uint8_t* data, const uint64_t* msg_offsets,
-                                    const uint64_t* msg_lengths, const uint64_t* offsets,
-                                    const uint64_t* host_offsets, uint64_t nbatches,
-                                    const uint32_t* pks, const uint32_t* sigs, uint64_t nitems,
-                                    const uint32_t* z16, const z_key_t& zkey, void* workspace,
-                                    uint32_t* kplane, bool hashed, int32_t* status,
-                                    uint64_t* fail_index, hipStream_t stream,
-                                    const uint32_t* skip_group_ok, const batch_votes_t* votes,
-                                    uint32_t* fuse_ctr, const input_gate_t* gate, uint32_t* done) {
-  // the fused launches hash the batch digest in the kernel: not for a call over the plane
-  if (fuse_ctr || gate || done) return hipErrorInvalidValue;
-  if (nbatches == 0) return hipSuccess;
-  if (nitems && !kplane) return hipErrorInvalidValue;
-  if (!hashed) {
-    const hipError_t he =
-        launch_strict_hram(data, msg_offsets, msg_lengths, pks, sigs, nitems, kplane, stream);
-    if (he != hipSuccess) return he;
-  }
-  return verify_batch_run(kplane, offsets, host_offsets, nbatches, pks, sigs, nitems, z16, zkey,
-                          workspace, status, fail_index, stream, nullptr, skip_group_ok,
-                          skip_group_ok ? 1 : 0, 1.0, nullptr, nullptr, nullptr, 0,
-                          skip_group_ok != nullptr, votes, true);
+hipError_t launch_verify_batch_msgs(batch_call_t call, const uint8_t* data,
+                                    const uint64_t* msg_offsets, const uint64_t* msg_lengths,
+                                    bool hashed, hipStream_t stream) {
+  call.kplane = true;
+  call.skip_per_group = call.skip_group_ok ? 1 : 0;
+  call.skip_pip = call.skip_group_ok != nullptr;
+  // refused before anything is queued (over the plane neither predicate is consulted)
+  hipError_t e = batch_call_check(call, false, false);
+  if (e == hipSuccess && !hashed && call.nbatches)
+    e = launch_strict_hram(data, msg_offsets, msg_lengths, call.pks, call.sigs, call.nitems,
+                           const_cast<uint32_t*>(call.digests), stream);
+  return e != hipSuccess ? e : verify_batch_run(call, stream);
 }
 
 size_t verify_batch_fuse_ctr_bytes() { return 4ull * kFuseCtr; }
@@ -3000,6 +2969,8 @@ hipError_t launch_cert_groups(const uint32_t* cert_digest, const uint64_t* cvo,
   pip_group_t grp{cvo, ncert, K, pre1, pre2, hdr_st, keys.vote_key, keys.ok, key_base, nkeys,
                   group_ok};
   const uint32_t pmin = kPipMin;   // smaller groups stay with the per-certificate path
+  batch_call_t gc;   // the groups as launch_pip's batches: offsets per group, no outputs
+  gc.digests = cert_digest, gc.offsets = gofs, gc.pks = pks, gc.sigs = sigs, gc.zkey = &zkey;
   auto gvotes = [&](uint64_t g) {
     return host_cvo[std::min((g + 1) * K, ncert)] - host_cvo[std::min(g * K, ncert)];
   };
@@ -3014,9 +2985,8 @@ hipError_t launch_cert_groups(const uint32_t* cert_digest, const uint64_t* cvo,
     if (votes > cap) return hipErrorInvalidValue;
     const uint64_t i0 = host_cvo[std::min(g * K, ncert)], i1 = host_cvo[std::min(e * K, ncert)];
     if (i1 > i0) {
-      const hipError_t pe = launch_pip(cert_digest, gofs, g, e, i0, i1, pmin, e - g, pmax, pks,
-                                       sigs, nullptr, zkey, w, nullptr, nullptr, grp, stream,
-                                       w.chunk_start);
+      const pip_slice_t ps{g, e, i0, i1, pmin, e - g, pmax, w.chunk_start, nullptr};
+      const hipError_t pe = launch_pip(gc, ps, w, grp, stream);
       if (pe != hipSuccess) return pe;
     }
     hipError_t err = hipGetLastError();

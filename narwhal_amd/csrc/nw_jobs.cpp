@@ -84,7 +84,8 @@ struct nw_job {
 namespace {
 
 using nw::rt::set_err;
-using nw::stage::a256;
+namespace stg = nw::stage;
+using stg::a256;
 
 constexpr int kMaxDev = 64;
 
@@ -524,9 +525,69 @@ int submit_strict(int dev, const uint8_t* digests, size_t digest_stride, const u
   return 0;
 }
 
-// offsets: nbatches + 1 host values from 0
-int submit_batch(int dev, const uint8_t* digests, const uint8_t* pks, const uint8_t* sigs,
-                 const uint64_t* offsets, size_t nbatches, const uint8_t* z16,
+// Registered signers on the device (DESIGN.md 5 "Round 12"): every vote of a verify_batch call
+// first takes the comb check under its registered key, and the batches all of whose votes pass are
+// settled before launch_verify_batch runs, which then skips them; a batch that is sent on runs
+// over the votes that did not pass only (DESIGN.md 5 "Round 14"; NW_BATCH_SIGNERS_VOTES=0, read
+// per call: over all its votes, as in round 12). The path needs the device's B comb; where that
+// cannot be had (no memory) the call runs as without a registry and no error is left behind, as
+// the keyed pipelines fall back (nw_api.cpp keyed_tables_or_fallback); any other failure is the
+// device's and is reported. With nothing registered nothing here adds a launch, an event wait, a
+// copy or a lock (one atomic load).
+int batch_signers_wanted(int dev, size_t nitems, const nw::ge_niels_pad** bcomb, bool* signers) {
+  *bcomb = nullptr;
+  *signers = nitems != 0 && nw::rt::signers_registered(dev) &&
+             nitems >= nw::batch_signers_min_votes();
+  if (!*signers) return 0;
+  const hipError_t eb = nw::bcomb_table(bcomb);
+  if (eb == hipErrorOutOfMemory) {
+    (void)hipGetLastError();
+    *signers = false;
+  } else if (eb != hipSuccess) {
+    return set_err(NW_E_DEVICE, "keyed B comb build", eb);
+  }
+  return 0;
+}
+
+// The comb phase of such a call, under the registry's read lease, which covers these launches
+// only; a registry cleared since batch_signers_wanted looked leaves the counters zero and no skip
+// list. digests: the batch digests, or (kplane) the call's k plane, hashed before. The votes'
+// states and lists live in the job's own scratch: the lease need not cover them.
+int batch_comb_phase(nw_job* j, const uint32_t* digests, bool kplane, const uint64_t* d_off,
+                     size_t nbatches, const uint32_t* d_pk, const uint32_t* d_sig, size_t nitems,
+                     const nw::ge_niels_pad* bcomb, void* scratch, unsigned long long* ctr,
+                     const uint32_t** batch_ok, nw::batch_votes_t* votes) {
+  nw::rt::SignersLease sl;
+  nw::strict_signers_t sg;
+  const int lrc = sl.acquire(j->dev, j->stream, &sg);
+  if (lrc < 0) return lrc;
+  if (lrc != 0) {
+    JOB_HIP(hipMemsetAsync(ctr, 0, 8 * kBstats, j->stream), "hipMemsetAsync (signers' counters)");
+    return 0;
+  }
+  const hipError_t se = nw::launch_batch_signers(
+      digests, d_off, nbatches, d_pk, d_sig, nitems, sg, bcomb, scratch, ctr, batch_ok, j->stream,
+      nw::batch_signers_votes() ? votes : nullptr, kplane);
+  const int rrc = sl.release();
+  JOB_HIP(se, kplane ? "verify_batch launch over messages (registered signers)"
+                     : "verify_batch launch (registered signers)");
+  return rrc;
+}
+
+// The per-vote messages of a verify_batch call over messages of any length (one offset and one
+// length per vote); the digest entry passes none.
+struct BatchMsgs {
+  const uint8_t* data;
+  const uint64_t *offsets, *lengths;
+};
+
+// offsets: nbatches + 1 host values from 0. msgs (dalek's verify_batch(messages, signatures,
+// public_keys)): the referenced bytes are packed contiguously (stg::pack_messages) and hashed into
+// the call's k plane, the job's own device memory beside its batch workspace (no lease), which
+// the comb phase and the batch launches then read in the digests' place. Such a call never takes
+// the fused launches, so none of the direct outputs, mapped inputs, gate or spin below.
+int submit_batch(int dev, const uint8_t* digests, const BatchMsgs* msgs, const uint8_t* pks,
+                 const uint8_t* sigs, const uint64_t* offsets, size_t nbatches, const uint8_t* z16,
                  int32_t* status_out, uint64_t* fail_index_out, nw_job** job) {
   const size_t nitems = nbatches ? offsets[nbatches] : 0;
   nw_job* j;
@@ -536,43 +597,21 @@ int submit_batch(int dev, const uint8_t* digests, const uint8_t* pks, const uint
     *job = j;
     return 0;
   }
-  const size_t m = nitems ? nitems : 1;
-  // Registered signers on the device (DESIGN.md 5 "Round 12"): every vote first takes the comb
-  // check under its registered key, and the batches all of whose votes pass are settled before
-  // launch_verify_batch runs, which then skips them; a batch that is sent on runs over the votes
-  // that did not pass only (DESIGN.md 5 "Round 14"; NW_BATCH_SIGNERS_VOTES=0, read per call:
-  // over all its votes, as in round 12). The path needs the device's B comb; where
-  // that cannot be had (no memory) the call runs as without a registry and no error is left
-  // behind. With nothing registered nothing here adds a launch, an event wait, a copy or a lock
-  // (one atomic load).
-  const nw::ge_niels_pad* bcomb = nullptr;
-  bool signers = nitems != 0 && nw::rt::signers_registered(dev) &&
-                 nitems >= nw::batch_signers_min_votes();
-  if (signers) {
-    // no memory for the table: without the path, as the keyed pipelines fall back
-    // (nw_api.cpp keyed_tables_or_fallback); any other failure is the device's and is reported
-    const hipError_t eb = nw::bcomb_table(&bcomb);
-    if (eb == hipErrorOutOfMemory) {
-      (void)hipGetLastError();
-      signers = false;
-    } else if (eb != hipSuccess) {
-      return job_abort(j, set_err(NW_E_DEVICE, "keyed B comb build", eb));
-    }
-  }
+  const nw::ge_niels_pad* bcomb;
+  bool signers;
+  rc = batch_signers_wanted(dev, nitems, &bcomb, &signers);
+  if (rc) return job_abort(j, rc);
   // a lone batch on the fused path: the launches write the verdict into the pinned buffer
   // (no copy back) and use the job's own counters (zero between calls); never with the comb
   // phase, whose skip list the fused launches do not read
-  const bool direct = !signers && nw::verify_batch_outputs_direct(nbatches, nitems);
-  const size_t o_d = 0, o_off = o_d + a256(32 * nbatches), o_pk = o_off + a256(8 * (nbatches + 1)),
-               o_sig = o_pk + a256(32 * m), o_z = o_sig + a256(64 * m),
-               o_st = o_z + (z16 ? a256(16 * m) : 0),
-               o_fi = o_st + a256(4 * nbatches),
-               o_dn = o_fi + a256(8 * nbatches),   // NW_BATCH_SPIN's done word
-               o_ct = o_dn + 256,                  // the comb phase's six counters
-               o_ws = o_ct + (signers ? 256 : 0),
-               o_sg = o_ws + a256(nw::batch_workspace_bytes(nbatches, nitems)),
-               end = o_sg + (signers ? a256(nw::batch_signers_bytes(nbatches, nitems)) : 0);
-  rc = job_reserve(j, o_ws, end);
+  const bool direct = !msgs && !signers && nw::verify_batch_outputs_direct(nbatches, nitems);
+  const stg::BatchOffs L = stg::plan_batch(
+      nbatches, nitems, msgs ? stg::messages_bytes(msgs->lengths, nitems) : stg::kNoMsgs,
+      z16 != nullptr, signers, nw::batch_workspace_bytes(nbatches, nitems),
+      signers ? nw::batch_signers_bytes(nbatches, nitems) : 0);
+  const size_t o_d = L.d, o_off = L.off, o_pk = L.pk, o_sig = L.sig, o_z = L.z, o_st = L.st,
+               o_fi = L.fi, o_dn = L.dn, o_ct = L.ct, o_ws = L.ws, o_sg = L.sg;
+  rc = job_reserve(j, o_ws, L.end);
   if (rc) return job_abort(j, rc);
   // A lone fused batch's inputs go straight from the caller's buffers into host-mapped
   // fine-grained device memory: no pinned staging copy, no H2D (NW_BATCH_VRAM=0: the pinned
@@ -587,7 +626,13 @@ int submit_batch(int dev, const uint8_t* digests, const uint8_t* pks, const uint
   const bool gate = vram && batch_gate() && nitems && nw::verify_batch_gate_ok(nbatches, nitems);
   char* const stage = vram ? j->vhost : j->hbuf;
   const auto ts0 = std::chrono::steady_clock::now();   // NW_BATCH_STAMPS (diagnostics)
-  memcpy(stage + o_d, digests, 32 * nbatches);
+  if (msgs) {
+    stg::pack_messages(stage + L.data, reinterpret_cast<uint64_t*>(stage + L.mo), msgs->data,
+                       msgs->offsets, msgs->lengths, nitems);
+    if (nitems) memcpy(stage + L.ml, msgs->lengths, 8 * nitems);
+  } else {
+    memcpy(stage + o_d, digests, 32 * nbatches);
+  }
   memcpy(stage + o_off, offsets, 8 * (nbatches + 1));
   if (nitems && !gate) {
     memcpy(stage + o_pk, pks, 32 * nitems);
@@ -659,45 +704,43 @@ int submit_batch(int dev, const uint8_t* digests, const uint8_t* pks, const uint
     // from here on a gated head may be queued (even if a later launch fails): the votes
     // and their flags are written whatever happens, so no wave is left waiting
     launched = gate;
-    // the comb phase under the registry's read lease, which covers these launches only; a
-    // registry cleared since the look above leaves the counters zero and no skip list
+    const uint64_t* const d_off = reinterpret_cast<const uint64_t*>(ibuf + o_off);
+    const uint32_t* const d_pk = reinterpret_cast<const uint32_t*>(ibuf + o_pk);
+    const uint32_t* const d_sig = reinterpret_cast<const uint32_t*>(ibuf + o_sig);
+    uint32_t* const kplane = reinterpret_cast<uint32_t*>(j->dbuf + L.kp);
+    if (msgs)
+      JOB_HIP(nw::launch_strict_hram(reinterpret_cast<const uint8_t*>(j->dbuf + L.data),
+                                     reinterpret_cast<const uint64_t*>(j->dbuf + L.mo),
+                                     reinterpret_cast<const uint64_t*>(j->dbuf + L.ml), d_pk, d_sig,
+                                     nitems, kplane, j->stream),
+              "k_strict_hram launch (verify_batch over messages)");
+    nw::batch_call_t call;
+    call.digests = msgs ? kplane : reinterpret_cast<const uint32_t*>(ibuf + o_d);
+    call.kplane = msgs != nullptr;
     const uint32_t* batch_ok = nullptr;
-    // the votes' states and lists live in the job's own scratch: the lease need not cover them
     nw::batch_votes_t votes{};
-    const bool leave_out = signers && nw::batch_signers_votes();
     if (signers) {
-      unsigned long long* const ctr = reinterpret_cast<unsigned long long*>(j->dbuf + o_ct);
-      nw::rt::SignersLease sl;
-      nw::strict_signers_t sg;
-      const int lrc = sl.acquire(dev, j->stream, &sg);
-      if (lrc < 0) return lrc;
-      if (lrc == 0) {
-        const hipError_t se = nw::launch_batch_signers(
-            reinterpret_cast<const uint32_t*>(ibuf + o_d),
-            reinterpret_cast<const uint64_t*>(ibuf + o_off), nbatches,
-            reinterpret_cast<const uint32_t*>(ibuf + o_pk),
-            reinterpret_cast<const uint32_t*>(ibuf + o_sig), nitems, sg, bcomb, j->dbuf + o_sg,
-            ctr, &batch_ok, j->stream, leave_out ? &votes : nullptr);
-        const int rrc = sl.release();
-        JOB_HIP(se, "verify_batch launch (registered signers)");
-        if (rrc) return rrc;
-      } else {
-        JOB_HIP(hipMemsetAsync(ctr, 0, 8 * kBstats, j->stream),
-                "hipMemsetAsync (signers' counters)");
-      }
+      const int crc = batch_comb_phase(
+          j, call.digests, call.kplane, d_off, nbatches, d_pk, d_sig, nitems, bcomb, j->dbuf + o_sg,
+          reinterpret_cast<unsigned long long*>(j->dbuf + o_ct), &batch_ok, &votes);
+      if (crc) return crc;
     }
-    const hipError_t e = nw::launch_verify_batch(
-        reinterpret_cast<const uint32_t*>(ibuf + o_d),
-        reinterpret_cast<const uint64_t*>(ibuf + o_off), h_off, nbatches,
-        reinterpret_cast<const uint32_t*>(ibuf + o_pk),
-        reinterpret_cast<const uint32_t*>(ibuf + o_sig), nitems,
-        z16 ? reinterpret_cast<const uint32_t*>(ibuf + o_z) : nullptr, key, j->dbuf + o_ws,
-        reinterpret_cast<int32_t*>(obuf + o_st), reinterpret_cast<uint64_t*>(obuf + o_fi),
-        j->stream, nullptr, batch_ok, batch_ok ? 1 : 0, 1.0, out_direct ? j->dfz : nullptr,
-        gate ? &gt : nullptr, done, dseq, batch_ok != nullptr,
-        batch_ok && votes.state ? &votes : nullptr);
+    call.offsets = d_off, call.host_offsets = h_off, call.nbatches = nbatches;
+    call.pks = d_pk, call.sigs = d_sig, call.nitems = nitems;
+    call.z16 = z16 ? reinterpret_cast<const uint32_t*>(ibuf + o_z) : nullptr;
+    call.zkey = &key;
+    call.status = reinterpret_cast<int32_t*>(obuf + o_st);
+    call.fail_index = reinterpret_cast<uint64_t*>(obuf + o_fi);
+    call.workspace = j->dbuf + o_ws;
+    call.skip_group_ok = batch_ok, call.skip_per_group = batch_ok ? 1 : 0;
+    call.skip_pip = batch_ok != nullptr;
+    call.votes = batch_ok && votes.state ? &votes : nullptr;
+    call.fuse_ctr = out_direct ? j->dfz : nullptr;
+    call.gate = gate ? &gt : nullptr;
+    call.done = done, call.done_seq = dseq;
+    const hipError_t e = nw::launch_verify_batch(call, j->stream);
     if (e != hipSuccess && out_direct) j->dfz_dirty = true;   // the head may have run
-    JOB_HIP(e, "verify_batch launch");
+    JOB_HIP(e, msgs ? "verify_batch launch over messages" : "verify_batch launch");
     return 0;
   });
   const auto ts2 = std::chrono::steady_clock::now();
@@ -741,28 +784,13 @@ int submit_sha(int dev, const uint8_t* data, const uint64_t* offsets, const uint
     *job = j;
     return 0;
   }
-  uint64_t total = 0;
-  for (size_t i = 0; i < n; ++i) total += lengths[i];
+  const uint64_t total = stg::messages_bytes(lengths, n);
   const size_t o_data = 0, o_off = a256(total ? total : 1), o_len = o_off + a256(8 * n),
                o_out = o_len + a256(8 * n), end = o_out + a256(32 * n);
   rc = job_reserve(j, end, end);
   if (rc) return job_abort(j, rc);
-  // Pack the referenced bytes contiguously (messages may live anywhere in `data`);
-  // contiguous runs are copied in one go.
-  uint64_t* offs = reinterpret_cast<uint64_t*>(j->hbuf + o_off);
-  uint64_t pos = 0;
-  for (size_t i = 0; i < n; ++i) {
-    offs[i] = pos;
-    pos += lengths[i];
-  }
-  size_t i = 0;
-  while (i < n) {
-    size_t k = i + 1;
-    while (k < n && offsets[k] == offsets[k - 1] + lengths[k - 1]) ++k;
-    const uint64_t bytes = offs[k - 1] + lengths[k - 1] - offs[i];
-    if (bytes) memcpy(j->hbuf + o_data + offs[i], data + offsets[i], bytes);
-    i = k;
-  }
+  stg::pack_messages(j->hbuf + o_data, reinterpret_cast<uint64_t*>(j->hbuf + o_off), data, offsets,
+                     lengths, n);
   memcpy(j->hbuf + o_len, lengths, 8 * n);
   rc = job_run(j, o_out, o_out, 32 * n, [&]() -> int {
     JOB_HIP(nw::launch_sha512_digest32(reinterpret_cast<const uint8_t*>(j->dbuf + o_data),
@@ -791,28 +819,15 @@ int submit_strict_msgs(int dev, const uint8_t* data, const uint64_t* offsets,
     *job = j;
     return 0;
   }
-  uint64_t total = 0;
-  for (size_t i = 0; i < n; ++i) total += lengths[i];
+  const uint64_t total = stg::messages_bytes(lengths, n);
   const size_t o_data = 0, o_off = a256(total ? total : 1), o_len = o_off + a256(8 * n),
                o_pk = o_len + a256(8 * n), o_sig = o_pk + a256(32 * n),
                o_st = o_sig + a256(64 * n), o_bm = o_st + a256(4 * n),
                end = o_bm + a256(8 * ((n + 63) / 64));
   rc = job_reserve(j, end, end);
   if (rc) return job_abort(j, rc);
-  uint64_t* offs = reinterpret_cast<uint64_t*>(j->hbuf + o_off);
-  uint64_t pos = 0;
-  for (size_t i = 0; i < n; ++i) {
-    offs[i] = pos;
-    pos += lengths[i];
-  }
-  size_t i = 0;
-  while (i < n) {   // contiguous runs are copied in one go
-    size_t k = i + 1;
-    while (k < n && offsets[k] == offsets[k - 1] + lengths[k - 1]) ++k;
-    const uint64_t bytes = offs[k - 1] + lengths[k - 1] - offs[i];
-    if (bytes) memcpy(j->hbuf + o_data + offs[i], data + offsets[i], bytes);
-    i = k;
-  }
+  stg::pack_messages(j->hbuf + o_data, reinterpret_cast<uint64_t*>(j->hbuf + o_off), data, offsets,
+                     lengths, n);
   memcpy(j->hbuf + o_len, lengths, 8 * n);
   memcpy(j->hbuf + o_pk, pks, 32 * n);
   memcpy(j->hbuf + o_sig, sigs, 64 * n);
@@ -840,127 +855,10 @@ int submit_strict_msgs(int dev, const uint8_t* data, const uint64_t* offsets,
   return 0;
 }
 
-// verify_batch over per-vote messages of any length (msg_offsets / msg_lengths: one entry per
-// vote): the referenced bytes packed contiguously and the offsets rebased as submit_strict_msgs
-// does, the batches staged as submit_batch does. The k plane (32 bytes per vote) is the job's own
-// device memory, beside its batch workspace: no lease. The registered signers serve the call as
-// they serve submit_batch: the comb phase reads the plane, hashed before it. Never the fused
-// launches, so none of submit_batch's direct outputs, mapped inputs, gate or spin.
-int submit_batch_msgs(int dev, const uint8_t* data, const uint64_t* msg_offsets,
-                      const uint64_t* msg_lengths, const uint8_t* pks, const uint8_t* sigs,
-                      const uint64_t* offsets, size_t nbatches, const uint8_t* z16,
-                      int32_t* status_out, uint64_t* fail_index_out, nw_job** job) {
-  const size_t nitems = nbatches ? offsets[nbatches] : 0;
-  nw_job* j;
-  int rc = job_acquire(dev, &j);
-  if (rc) return rc;
-  if (nbatches == 0) {
-    *job = j;
-    return 0;
-  }
-  const size_t m = nitems ? nitems : 1;
-  const nw::ge_niels_pad* bcomb = nullptr;
-  bool signers = nitems != 0 && nw::rt::signers_registered(dev) &&
-                 nitems >= nw::batch_signers_min_votes();
-  if (signers) {   // as submit_batch: no memory for the B comb = without the path
-    const hipError_t eb = nw::bcomb_table(&bcomb);
-    if (eb == hipErrorOutOfMemory) {
-      (void)hipGetLastError();
-      signers = false;
-    } else if (eb != hipSuccess) {
-      return job_abort(j, set_err(NW_E_DEVICE, "keyed B comb build", eb));
-    }
-  }
-  uint64_t total = 0;
-  for (size_t i = 0; i < nitems; ++i) total += msg_lengths[i];
-  const size_t o_data = 0, o_mo = a256(total ? total : 1), o_ml = o_mo + a256(8 * m),
-               o_off = o_ml + a256(8 * m), o_pk = o_off + a256(8 * (nbatches + 1)),
-               o_sig = o_pk + a256(32 * m), o_z = o_sig + a256(64 * m),
-               o_st = o_z + (z16 ? a256(16 * m) : 0), o_fi = o_st + a256(4 * nbatches),
-               o_ct = o_fi + a256(8 * nbatches),   // the comb phase's six counters
-               o_ws = o_ct + (signers ? 256 : 0),
-               o_kp = o_ws + a256(nw::batch_workspace_bytes(nbatches, nitems)),
-               o_sg = o_kp + a256(32 * m),
-               end = o_sg + (signers ? a256(nw::batch_signers_bytes(nbatches, nitems)) : 0);
-  rc = job_reserve(j, o_ws, end);
-  if (rc) return job_abort(j, rc);
-  uint64_t* offs = reinterpret_cast<uint64_t*>(j->hbuf + o_mo);
-  uint64_t pos = 0;
-  for (size_t i = 0; i < nitems; ++i) {
-    offs[i] = pos;
-    pos += msg_lengths[i];
-  }
-  size_t i = 0;
-  while (i < nitems) {   // contiguous runs are copied in one go
-    size_t k = i + 1;
-    while (k < nitems && msg_offsets[k] == msg_offsets[k - 1] + msg_lengths[k - 1]) ++k;
-    const uint64_t bytes = offs[k - 1] + msg_lengths[k - 1] - offs[i];
-    if (bytes) memcpy(j->hbuf + o_data + offs[i], data + msg_offsets[i], bytes);
-    i = k;
-  }
-  memcpy(j->hbuf + o_off, offsets, 8 * (nbatches + 1));
-  if (nitems) {
-    memcpy(j->hbuf + o_ml, msg_lengths, 8 * nitems);
-    memcpy(j->hbuf + o_pk, pks, 32 * nitems);
-    memcpy(j->hbuf + o_sig, sigs, 64 * nitems);
-    if (z16) memcpy(j->hbuf + o_z, z16, 16 * nitems);
-  }
-  nw::z_key_t key;
-  rc = fill_key(key);
-  if (rc) return job_abort(j, rc);
-  rc = job_run(j, o_st, o_st, o_ws - o_st, [&]() -> int {
-    const uint32_t* const d_pk = reinterpret_cast<const uint32_t*>(j->dbuf + o_pk);
-    const uint32_t* const d_sig = reinterpret_cast<const uint32_t*>(j->dbuf + o_sig);
-    const uint64_t* const d_off = reinterpret_cast<const uint64_t*>(j->dbuf + o_off);
-    uint32_t* const kplane = reinterpret_cast<uint32_t*>(j->dbuf + o_kp);
-    JOB_HIP(nw::launch_strict_hram(reinterpret_cast<const uint8_t*>(j->dbuf + o_data),
-                                   reinterpret_cast<const uint64_t*>(j->dbuf + o_mo),
-                                   reinterpret_cast<const uint64_t*>(j->dbuf + o_ml), d_pk, d_sig,
-                                   nitems, kplane, j->stream),
-            "k_strict_hram launch (verify_batch over messages)");
-    const uint32_t* batch_ok = nullptr;
-    nw::batch_votes_t votes{};
-    const bool leave_out = signers && nw::batch_signers_votes();
-    if (signers) {
-      unsigned long long* const ctr = reinterpret_cast<unsigned long long*>(j->dbuf + o_ct);
-      nw::rt::SignersLease sl;
-      nw::strict_signers_t sg;
-      const int lrc = sl.acquire(dev, j->stream, &sg);
-      if (lrc < 0) return lrc;
-      if (lrc == 0) {
-        const hipError_t se = nw::launch_batch_signers(
-            kplane, d_off, nbatches, d_pk, d_sig, nitems, sg, bcomb, j->dbuf + o_sg, ctr,
-            &batch_ok, j->stream, leave_out ? &votes : nullptr, true);
-        const int rrc = sl.release();
-        JOB_HIP(se, "verify_batch launch over messages (registered signers)");
-        if (rrc) return rrc;
-      } else {
-        JOB_HIP(hipMemsetAsync(ctr, 0, 8 * kBstats, j->stream),
-                "hipMemsetAsync (signers' counters)");
-      }
-    }
-    JOB_HIP(nw::launch_verify_batch_msgs(
-                nullptr, nullptr, nullptr, d_off, offsets, nbatches, d_pk, d_sig, nitems,
-                z16 ? reinterpret_cast<const uint32_t*>(j->dbuf + o_z) : nullptr, key,
-                j->dbuf + o_ws, kplane, true, reinterpret_cast<int32_t*>(j->dbuf + o_st),
-                reinterpret_cast<uint64_t*>(j->dbuf + o_fi), j->stream, batch_ok,
-                batch_ok && votes.state ? &votes : nullptr),
-            "verify_batch launch over messages");
-    return 0;
-  });
-  if (rc) return job_abort(j, rc);
-  job_out(j, status_out, o_st, 4 * nbatches);
-  job_out(j, fail_index_out, o_fi, 8 * nbatches);
-  if (signers) j->bstats = reinterpret_cast<const uint64_t*>(j->hbuf + o_ct);
-  *job = j;
-  return 0;
-}
-
 // ---- primary messages ------------------------------------------------------------------
 // The sections of a job's staging buffers (pinned and device share one layout): nw_stage.hpp
 // states the committee's, the header stream's, the certificate votes' and the Vote messages';
 // what follows them (slots, statuses, indices, flags, workspace) is each job's own.
-namespace stg = nw::stage;
 using stg::Packer;
 
 // The staged arrays as the kernels' structs take them (words where the public structs say
@@ -1696,6 +1594,79 @@ int nw::rt::wire_verify_device(int dev, const nw_committee* com, const uint8_t* 
   return 0;
 }
 
+// The batch offsets of nw_submit_verify_batch_many / _msgs: from 0, monotone; per_vote: the
+// per-vote arrays are all there (needed once a batch has a vote).
+int check_batch_offsets(const uint64_t* offsets, size_t nbatches, bool per_vote) {
+  if (nbatches == 0) return 0;
+  if (!offsets) return set_err(NW_E_INVALID_ARG, "null pointer");
+  if (offsets[0] != 0) return set_err(NW_E_INVALID_ARG, "offsets[0] must be 0");
+  for (size_t b = 0; b < nbatches; ++b)
+    if (offsets[b + 1] < offsets[b]) return set_err(NW_E_INVALID_ARG, "offsets not monotone");
+  if (offsets[nbatches] && !per_vote) return set_err(NW_E_INVALID_ARG, "null pointer");
+  return 0;
+}
+
+// Both verify_batch submits: one device, or whole batches per part with about equal votes (+1 per
+// batch for its fixed tail); each part's offsets are rebased and its votes, message ranges and
+// z16 start at its first vote (the ranges stay offsets into msgs->data).
+template <class Check>
+int submit_batch_entry(Check check, const uint8_t* digests, const BatchMsgs* msgs,
+                       const uint8_t* pks, const uint8_t* sigs, const uint64_t* offsets,
+                       size_t nbatches, const uint8_t* z16, int32_t* status_out,
+                       uint64_t* fail_index_out, nw_job** job) {
+  const auto one = [&](int dev) {
+    return submit_batch(dev, digests, msgs, pks, sigs, offsets, nbatches, z16, status_out,
+                        fail_index_out, job);
+  };
+  const auto many = [&](const std::vector<int>& devs) {
+    std::vector<uint64_t> w(nbatches + 1);
+    for (size_t b = 0; b <= nbatches; ++b) w[b] = offsets[b] + b;
+    return fan_out(devs, weighted_bounds(nbatches, devs.size(), w),
+                   [&](int dev, size_t a, size_t e, nw_job** sub) {
+                     std::vector<uint64_t> off(e - a + 1);
+                     for (size_t b = a; b <= e; ++b) off[b - a] = offsets[b] - offsets[a];
+                     const uint64_t v0 = offsets[a];
+                     BatchMsgs pm{};
+                     if (msgs)
+                       pm = BatchMsgs{msgs->data, msgs->offsets ? msgs->offsets + v0 : nullptr,
+                                      msgs->lengths ? msgs->lengths + v0 : nullptr};
+                     return submit_batch(dev, digests ? digests + 32 * a : nullptr,
+                                         msgs ? &pm : nullptr, pks ? pks + 32 * v0 : nullptr,
+                                         sigs ? sigs + 64 * v0 : nullptr, off.data(), e - a,
+                                         z16 ? z16 + 16 * v0 : nullptr,
+                                         status_out ? status_out + a : nullptr,
+                                         fail_index_out ? fail_index_out + a : nullptr, sub);
+                   },
+                   job);
+  };
+  return submit_entry(job, check, one, many);
+}
+
+// ---- blocking host-buffer entry points = submit + wait ------------------------------
+static int run_blocking(int rc, nw_job* j) {
+  if (rc) return rc;
+  const auto t0 = std::chrono::steady_clock::now();
+  rc = nw_job_wait(j);
+  if (batch_stamps())
+    fprintf(stderr, "[narwhal_amd] wait %.1f us\n",
+            std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0)
+                .count());
+  nw_job_release(j);
+  return rc;
+}
+
+// One batch of n votes through many(offsets, &status, &index); no votes: dalek's MSM of [0]B, Ok.
+template <class Many>
+static int run_one_batch(size_t n, size_t* fail_index, Many many) {
+  const uint64_t offs[2] = {0, n};
+  int32_t st = 0;
+  uint64_t fi = 0;
+  const int rc = n ? many(offs, &st, &fi) : nw::rt::ensure_init();
+  if (rc) return rc;
+  if (fail_index) *fail_index = (size_t)fi;
+  return st;
+}
+
 extern "C" {
 
 int nw_submit_verify_strict(const uint8_t* digests, size_t digest_stride, const uint8_t* pks,
@@ -1754,38 +1725,11 @@ int nw_submit_verify_batch_many(const uint8_t* digests, const uint8_t* pks, cons
                                 const uint64_t* offsets, size_t nbatches, const uint8_t* z16,
                                 int32_t* status_out, uint64_t* fail_index_out, nw_job** job) {
   const auto check = [&]() -> int {
-    if (nbatches && (!digests || !offsets)) return set_err(NW_E_INVALID_ARG, "null pointer");
-    if (nbatches) {
-      if (offsets[0] != 0) return set_err(NW_E_INVALID_ARG, "offsets[0] must be 0");
-      for (size_t b = 0; b < nbatches; ++b)
-        if (offsets[b + 1] < offsets[b]) return set_err(NW_E_INVALID_ARG, "offsets not monotone");
-    }
-    const size_t nitems = nbatches ? offsets[nbatches] : 0;
-    if (nitems && (!pks || !sigs)) return set_err(NW_E_INVALID_ARG, "null pointer");
-    return 0;
+    if (nbatches && !digests) return set_err(NW_E_INVALID_ARG, "null pointer");
+    return check_batch_offsets(offsets, nbatches, pks && sigs);
   };
-  const auto one = [&](int dev) {
-    return submit_batch(dev, digests, pks, sigs, offsets, nbatches, z16, status_out,
-                        fail_index_out, job);
-  };
-  const auto many = [&](const std::vector<int>& devs) {
-    // whole batches per part, about equal votes (+1 per batch for its fixed tail)
-    std::vector<uint64_t> w(nbatches + 1);
-    for (size_t b = 0; b <= nbatches; ++b) w[b] = offsets[b] + b;
-    return fan_out(devs, weighted_bounds(nbatches, devs.size(), w),
-                   [&](int dev, size_t a, size_t e, nw_job** sub) {
-                     std::vector<uint64_t> off(e - a + 1);
-                     for (size_t b = a; b <= e; ++b) off[b - a] = offsets[b] - offsets[a];
-                     const uint64_t v0 = offsets[a];
-                     return submit_batch(dev, digests + 32 * a, pks ? pks + 32 * v0 : nullptr,
-                                         sigs ? sigs + 64 * v0 : nullptr, off.data(), e - a,
-                                         z16 ? z16 + 16 * v0 : nullptr,
-                                         status_out ? status_out + a : nullptr,
-                                         fail_index_out ? fail_index_out + a : nullptr, sub);
-                   },
-                   job);
-  };
-  return submit_entry(job, check, one, many);
+  return submit_batch_entry(check, digests, nullptr, pks, sigs, offsets, nbatches, z16, status_out,
+                            fail_index_out, job);
 }
 
 int nw_submit_verify_batch_msgs(const uint8_t* data, const uint64_t* msg_offsets,
@@ -1793,44 +1737,16 @@ int nw_submit_verify_batch_msgs(const uint8_t* data, const uint64_t* msg_offsets
                                 const uint8_t* sigs, const uint64_t* offsets, size_t nbatches,
                                 const uint8_t* z16, int32_t* status_out,
                                 uint64_t* fail_index_out, nw_job** job) {
+  const BatchMsgs msgs{data, msg_offsets, msg_lengths};
   const auto check = [&]() -> int {
-    if (nbatches && !offsets) return set_err(NW_E_INVALID_ARG, "null pointer");
-    if (nbatches) {
-      if (offsets[0] != 0) return set_err(NW_E_INVALID_ARG, "offsets[0] must be 0");
-      for (size_t b = 0; b < nbatches; ++b)
-        if (offsets[b + 1] < offsets[b]) return set_err(NW_E_INVALID_ARG, "offsets not monotone");
-    }
-    const size_t nitems = nbatches ? offsets[nbatches] : 0;
-    if (nitems && (!pks || !sigs || !msg_offsets || !msg_lengths))
-      return set_err(NW_E_INVALID_ARG, "null pointer");
+    const int rc = check_batch_offsets(offsets, nbatches, pks && sigs && msg_offsets && msg_lengths);
+    const size_t nitems = !rc && nbatches ? offsets[nbatches] : 0;
     for (size_t i = 0; i < nitems && !data; ++i)   // only empty messages need no data
       if (msg_lengths[i]) return set_err(NW_E_INVALID_ARG, "null pointer");
-    return 0;
+    return rc;
   };
-  const auto one = [&](int dev) {
-    return submit_batch_msgs(dev, data, msg_offsets, msg_lengths, pks, sigs, offsets, nbatches,
-                             z16, status_out, fail_index_out, job);
-  };
-  const auto many = [&](const std::vector<int>& devs) {
-    // whole batches per part, about equal votes (+1 per batch for its fixed tail); each part's
-    // votes, message ranges and z16 start at its first vote (the ranges stay offsets into data)
-    std::vector<uint64_t> w(nbatches + 1);
-    for (size_t b = 0; b <= nbatches; ++b) w[b] = offsets[b] + b;
-    return fan_out(devs, weighted_bounds(nbatches, devs.size(), w),
-                   [&](int dev, size_t a, size_t e, nw_job** sub) {
-                     std::vector<uint64_t> off(e - a + 1);
-                     for (size_t b = a; b <= e; ++b) off[b - a] = offsets[b] - offsets[a];
-                     const uint64_t v0 = offsets[a];
-                     return submit_batch_msgs(
-                         dev, data, msg_offsets ? msg_offsets + v0 : nullptr,
-                         msg_lengths ? msg_lengths + v0 : nullptr, pks ? pks + 32 * v0 : nullptr,
-                         sigs ? sigs + 64 * v0 : nullptr, off.data(), e - a,
-                         z16 ? z16 + 16 * v0 : nullptr, status_out ? status_out + a : nullptr,
-                         fail_index_out ? fail_index_out + a : nullptr, sub);
-                   },
-                   job);
-  };
-  return submit_entry(job, check, one, many);
+  return submit_batch_entry(check, nullptr, &msgs, pks, sigs, offsets, nbatches, z16, status_out,
+                            fail_index_out, job);
 }
 
 int nw_submit_sha512_digest32_many(const uint8_t* data, const uint64_t* offsets,
@@ -2144,19 +2060,6 @@ int nw_path_stats(uint64_t* small_jobs, uint64_t* pipeline_jobs) {
   return 0;
 }
 
-// ---- blocking host-buffer entry points = submit + wait ------------------------------
-static int run_blocking(int rc, nw_job* j) {
-  if (rc) return rc;
-  const auto t0 = std::chrono::steady_clock::now();
-  rc = nw_job_wait(j);
-  if (batch_stamps())
-    fprintf(stderr, "[narwhal_amd] wait %.1f us\n",
-            std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0)
-                .count());
-  nw_job_release(j);
-  return rc;
-}
-
 int nw_sha512_digest32_many(const uint8_t* data, const uint64_t* offsets,
                             const uint64_t* lengths, size_t n, uint8_t* out32) {
   nw_job* j = nullptr;
@@ -2186,26 +2089,6 @@ int nw_signature_verify(const uint8_t sig[64], const uint8_t digest[32], const u
   return rc ? rc : st;
 }
 
-int nw_signature_verify_batch(const uint8_t digest[32], const uint8_t* pks, const uint8_t* sigs,
-                              size_t n, const uint8_t* z16, size_t* fail_index) {
-  if (!digest || (n && (!pks || !sigs))) return set_err(NW_E_INVALID_ARG, "null pointer");
-  if (n == 0) {   // crypto::verify_batch over no votes: dalek MSM of [0]B -> Ok
-    int rc = nw::rt::ensure_init();
-    if (rc) return rc;
-    if (fail_index) *fail_index = 0;
-    return NW_OK;
-  }
-  const uint64_t offs[2] = {0, n};
-  int32_t st = 0;
-  uint64_t fi = 0;
-  nw_job* j = nullptr;
-  int rc = run_blocking(nw_submit_verify_batch_many(digest, pks, sigs, offs, 1, z16, &st, &fi, &j),
-                        j);
-  if (rc) return rc;
-  if (fail_index) *fail_index = (size_t)fi;
-  return st;
-}
-
 int nw_verify_batch_many(const uint8_t* digests, const uint8_t* pks, const uint8_t* sigs,
                          const uint64_t* offsets, size_t nbatches, const uint8_t* z16,
                          int32_t* status_out) {
@@ -2231,24 +2114,24 @@ int nw_verify_batch_msgs_many(const uint8_t* data, const uint64_t* msg_offsets,
                       j);
 }
 
+int nw_signature_verify_batch(const uint8_t digest[32], const uint8_t* pks, const uint8_t* sigs,
+                              size_t n, const uint8_t* z16, size_t* fail_index) {
+  if (!digest || (n && (!pks || !sigs))) return set_err(NW_E_INVALID_ARG, "null pointer");
+  return run_one_batch(n, fail_index, [&](const uint64_t* offs, int32_t* st, uint64_t* fi) {
+    nw_job* j = nullptr;
+    const int rc = nw_submit_verify_batch_many(digest, pks, sigs, offs, 1, z16, st, fi, &j);
+    return run_blocking(rc, j);
+  });
+}
+
 int nw_signature_verify_batch_msgs(const uint8_t* data, const uint64_t* msg_offsets,
                                    const uint64_t* msg_lengths, const uint8_t* pks,
                                    const uint8_t* sigs, size_t n, const uint8_t* z16,
                                    size_t* fail_index) {
-  if (n == 0) {   // no votes: Ok, as nw_signature_verify_batch
-    int rc = nw::rt::ensure_init();
-    if (rc) return rc;
-    if (fail_index) *fail_index = 0;
-    return NW_OK;
-  }
-  const uint64_t offs[2] = {0, n};
-  int32_t st = 0;
-  uint64_t fi = 0;
-  const int rc = nw_verify_batch_msgs_many(data, msg_offsets, msg_lengths, pks, sigs, offs, 1,
-                                           z16, &st, &fi);
-  if (rc) return rc;
-  if (fail_index) *fail_index = (size_t)fi;
-  return st;
+  return run_one_batch(n, fail_index, [&](const uint64_t* offs, int32_t* st, uint64_t* fi) {
+    return nw_verify_batch_msgs_many(data, msg_offsets, msg_lengths, pks, sigs, offs, 1, z16, st,
+                                     fi);
+  });
 }
 
 int nw_certificates_verify_many(const nw_committee* committee, const nw_certificates* certs,

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "narwhal_amd.h"
+#include "nw_batch_call.hpp"
 #include "nw_strict_layout.hpp"
 #include "nw_strict_keymajor.hpp"
 
@@ -286,34 +287,11 @@ bool verify_batch_outputs_direct(uint64_t nbatches, uint64_t nitems);
 // a zeroed device array of this size (fuse_ctr, e.g. shipped with its inputs' H2D copy),
 // which saves the kernel that would zero them.
 size_t verify_batch_fuse_ctr_bytes();
-// Input gate of a lone fused batch whose inputs the CPU is still writing into host-mapped
-// device memory when the launch is queued (nw_jobs.cpp submit_batch): the head's vote waves
-// wait until flags[vote / chunk] == seq (a system-scope load, then a system-scope acquire),
-// so the kernels start while the bytes are in flight. digests and offsets must be written
-// before the launch. verify_batch_gate_ok: the batch takes the fused head (the only launch
-// that honours the gate). chunk: a multiple of 64 votes.
-struct input_gate_t {
-  const uint32_t* flags;
-  uint32_t seq;
-  uint32_t chunk;
-};
+// verify_batch_gate_ok: the batch takes the fused head, the only launch that honours an input
+// gate (nw_batch_call.hpp input_gate_t).
 bool verify_batch_gate_ok(uint64_t nbatches, uint64_t nitems);
-// done (optional, host-mapped; lone fused batches only, verify_batch_outputs_direct): the
-// fused tail stores done_seq there (system scope) right after the verdict, so a host may
-// spin on it instead of waiting for the launch's completion signal.
-// skip_group_ok (optional, device): batch b is settled (status Ok) when
-// skip_group_ok[b / skip_per_group] != 0 (launch_cert_groups, launch_votes_keyed);
-// active_frac: the caller's estimate of the fraction of votes not skipped (chunk sizing).
-// skip_pip: with a skip list, batches of Pippenger size still take the Pippenger kernels, which
-// then honour the list (launch_batch_signers' callers); a lone large batch takes the separate
-// kernels, never the fused launches, so fuse_ctr, gate and done must be null. Without it no batch
-// of a call with a skip list takes the Pippenger path (the certificate callers).
-// votes (optional; with skip_pip, skip_per_group = 1, no key tables): the comb phase's verdict
-// per vote (launch_batch_signers, DESIGN.md 5 "Round 14"). A vote whose state is kVotePass adds
-// nothing to the sum of its batch for any coefficient set and cannot fail a check that comes
-// before the sum, so a batch that is sent on runs over its other votes only, each at its own
-// position: the items are built from `list`, the Straus ladder runs over the chunks that hold
-// a listed vote, and in a Pippenger batch a passed vote is neutral and not decompressed.
+// The comb phase's verdict per vote, as launch_batch_signers fills it and a batch_call_t's
+// `votes` hands it on.
 struct batch_votes_t {
   const uint32_t* state;   // one word per vote of the call (nw_strict.hpp kVotePass ...)
   const uint32_t* list;    // the votes whose state is not kVotePass, dense, in any order
@@ -321,48 +299,22 @@ struct batch_votes_t {
   uint32_t* live;          // nitems words: a slice's chunks that hold a listed vote
   uint32_t* nlive;         // their number (device; cleared per slice)
 };
-hipError_t launch_verify_batch(const uint32_t* digests, const uint64_t* offsets,
-                               const uint64_t* host_offsets, uint64_t nbatches,
-                               const uint32_t* pks, const uint32_t* sigs, uint64_t nitems,
-                               const uint32_t* z16, const z_key_t& zkey, void* workspace,
-                               int32_t* status, uint64_t* fail_index, hipStream_t stream,
-                               const key_tables_t* keys = nullptr,
-                               const uint32_t* skip_group_ok = nullptr,
-                               uint64_t skip_per_group = 0, double active_frac = 1.0,
-                               uint32_t* fuse_ctr = nullptr,
-                               const input_gate_t* gate = nullptr,
-                               uint32_t* done = nullptr, uint32_t done_seq = 0,
-                               bool skip_pip = false,
-                               const batch_votes_t* votes = nullptr);
+// The one launcher: every field of the call is described in nw_batch_call.hpp, and
+// batch_call_check there says which combinations are refused (hipErrorInvalidValue).
+hipError_t launch_verify_batch(const batch_call_t& call, hipStream_t stream);
 // verify_batch over per-vote messages of any length (dalek's verify_batch(messages, signatures,
 // public_keys)): vote i's message is msg_lengths[i] bytes at data + msg_offsets[i] (device
-// arrays, one entry per vote of the call, any alignment). k_strict_hram (launch_strict_hram) runs
-// once over all nitems votes of the call, before the slice loop, and writes k_i = SHA-512(R_i ||
-// A_i || M_i) mod l into kplane + 8 i; one lane per vote, a wave runs as long as its longest
-// message. Then launch_verify_batch's plan / expand / items / chunks / combine sequence and the
-// Pippenger kernels run with the instances that read k from the plane at the call-global vote
-// index (k_bv_items_k, k_bv_items_listed_k, k_pip_points_k) instead of hashing the batch digest.
-// kplane: 32 bytes per vote of memory the caller owns (a job's own device buffer, the nw_dev_*
-// caller's workspace): not a shared per-device buffer, so it needs no lease and two streams
-// cannot collide on it. hashed: the caller has already run launch_strict_hram on `stream` (the
-// comb phase reads the plane first). skip_group_ok / votes: launch_batch_signers' outputs, as
-// launch_verify_batch takes them with skip_per_group = 1 and skip_pip. Never the fused head (it
-// hashes the batch digest in the kernel and the input gate belongs to it) and, by choice, not the
-// fused tail either: a lone large batch runs k_pip_points_k, k_pip_sort and the separate tail
-// kernels, as a skip_pip call does; fuse_ctr, gate and done are refused (hipErrorInvalidValue).
-// Out of scope: k_bv_items_chunked (certificate callers only), the certificate groups, the keyed
-// (key_tables_t) path.
-hipError_t launch_verify_batch_msgs(const uint8_t* data, const uint64_t* msg_offsets,
-                                    const uint64_t* msg_lengths, const uint64_t* offsets,
-                                    const uint64_t* host_offsets, uint64_t nbatches,
-                                    const uint32_t* pks, const uint32_t* sigs, uint64_t nitems,
-                                    const uint32_t* z16, const z_key_t& zkey, void* workspace,
-                                    uint32_t* kplane, bool hashed, int32_t* status,
-                                    uint64_t* fail_index, hipStream_t stream,
-                                    const uint32_t* skip_group_ok = nullptr,
-                                    const batch_votes_t* votes = nullptr,
-                                    uint32_t* fuse_ctr = nullptr,
-                                    const input_gate_t* gate = nullptr, uint32_t* done = nullptr);
+// arrays, one entry per vote of the call, any alignment). call.digests is the caller's k plane
+// (32 bytes per vote: a job's own device buffer, the nw_dev_* caller's workspace; not a shared
+// per-device buffer, so it needs no lease). Unless `hashed` (the caller has already run
+// launch_strict_hram on `stream`: the comb phase reads the plane first), k_strict_hram runs once
+// over all votes of the call, before the slice loop; then launch_verify_batch runs over the
+// plane (kplane), with call.skip_group_ok / votes as launch_batch_signers left them
+// (skip_per_group = 1, skip_pip). A lone large batch runs k_pip_points_k, k_pip_sort and the
+// separate tail kernels, as a skip_pip call does.
+hipError_t launch_verify_batch_msgs(batch_call_t call, const uint8_t* data,
+                                    const uint64_t* msg_offsets, const uint64_t* msg_lengths,
+                                    bool hashed, hipStream_t stream);
 // Signature::verify_batch under the registered signers (nw_kernels.hip, DESIGN.md 5 "Round 12"):
 // every vote of the call through the comb check under its registered key (sg.n != 0; bcomb: the
 // device's B comb), the parities in batched inversions; *batch_ok_out (in scratch, nbatches words)

@@ -174,5 +174,74 @@ inline VoteMsgs view_vote_msgs(const char* base, const VoteMsgOffs& o, size_t n)
                   at<uint8_t>(base, o.au), at<uint8_t>(base, o.sg),  n};
 }
 
+// ---- per-item messages of any length (the SHA-512, strict and verify_batch jobs) -----------
+// Message i is lengths[i] bytes at data + offsets[i]: anywhere in `data`, in any order,
+// overlapping or not. The jobs stage them packed in item order: offs_out[i] = the bytes before
+// message i, and dst gets the bytes (runs that are contiguous in `data` in one copy). data may
+// be null when every message is empty. messages_bytes: what dst must hold.
+inline uint64_t messages_bytes(const uint64_t* lengths, size_t n) {
+  uint64_t total = 0;
+  for (size_t i = 0; i < n; ++i) total += lengths[i];
+  return total;
+}
+inline void pack_messages(char* dst, uint64_t* offs_out, const uint8_t* data,
+                          const uint64_t* offsets, const uint64_t* lengths, size_t n) {
+  uint64_t pos = 0;
+  for (size_t i = 0; i < n; ++i) {
+    offs_out[i] = pos;
+    pos += lengths[i];
+  }
+  size_t i = 0;
+  while (i < n) {
+    size_t k = i + 1;
+    while (k < n && offsets[k] == offsets[k - 1] + lengths[k - 1]) ++k;
+    const uint64_t bytes = offs_out[k - 1] + lengths[k - 1] - offs_out[i];
+    if (bytes) memcpy(dst + offs_out[i], data + offsets[i], bytes);
+    i = k;
+  }
+}
+
+// ---- a verify_batch job (nw_jobs.cpp submit_batch) ----------------------------------------
+// The inputs are [0, st): the batch digests, or for a call over per-vote messages
+// (msg_bytes != kNoMsgs) the packed bytes with their offsets and lengths; then the vote offsets,
+// keys, signatures and (z16) coefficients. The outputs are [st, ws): statuses, failing indices,
+// a digest call's done word (NW_BATCH_SPIN; a lone fused batch's input-gate flags sit at `st` of
+// its device-memory buffer instead) and, with `signers`, the comb phase's six counters. Device
+// only from `ws` on: the batch workspace (ws_bytes), a message call's k plane (32 bytes per
+// vote), the comb phase's scratch (sg_bytes). A section a call does not have is empty.
+constexpr size_t kNoMsgs = ~(size_t)0;
+struct BatchOffs {
+  size_t data, mo, ml, d, off, pk, sig, z, st, fi, dn, ct, ws, kp, sg, end;
+};
+inline BatchOffs plan_batch(size_t nbatches, size_t nitems, size_t msg_bytes, bool z16,
+                            bool signers, size_t ws_bytes, size_t sg_bytes) {
+  const bool msgs = msg_bytes != kNoMsgs;
+  const size_t m = nitems ? nitems : 1;
+  size_t o = 0;
+  const auto sec = [&o](bool present, size_t bytes) {
+    const size_t at = o;
+    if (present) o += a256(bytes);
+    return at;
+  };
+  BatchOffs p;
+  p.data = sec(msgs, msg_bytes ? msg_bytes : 1);
+  p.mo = sec(msgs, 8 * m);
+  p.ml = sec(msgs, 8 * m);
+  p.d = sec(!msgs, 32 * nbatches);
+  p.off = sec(true, 8 * (nbatches + 1));
+  p.pk = sec(true, 32 * m);
+  p.sig = sec(true, 64 * m);
+  p.z = sec(z16, 16 * m);
+  p.st = sec(true, 4 * nbatches);
+  p.fi = sec(true, 8 * nbatches);
+  p.dn = sec(!msgs, 256);
+  p.ct = sec(signers, 256);
+  p.ws = sec(true, ws_bytes);
+  p.kp = sec(msgs, 32 * m);
+  p.sg = sec(signers, sg_bytes);
+  p.end = o;
+  return p;
+}
+
 }  // namespace stage
 }  // namespace nw
