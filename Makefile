@@ -59,13 +59,13 @@ oracle:
 	$(MAKE) -s -C oracle
 
 hostcheck: tools/libnw_hostcheck.so
-tools/libnw_hostcheck.so: tools/hostcheck.hip tools/limb_ops.hpp $(HDRS)
+tools/libnw_hostcheck.so: tools/hostcheck.hip tools/limb_ops.hpp tools/sc_ops.hpp $(HDRS)
 	$(HIPCC) --cuda-host-only -O2 -std=c++17 -fPIC -shared -Iinclude $< -o $@
 
 # the per-lane field / point routines and the limb-parallel ones (nw_lp.hpp) as gfx950 kernels
 # over raw limbs (tests/test_gpu_field_limbs.py); a library of its own, not linked into $(LIB)
 lpcheck: tools/libnw_lpcheck.so
-tools/libnw_lpcheck.so: tools/lpcheck.hip tools/limb_ops.hpp $(HDRS)
+tools/libnw_lpcheck.so: tools/lpcheck.hip tools/limb_ops.hpp tools/sc_ops.hpp $(HDRS)
 	$(HIPCC) -O3 -std=c++17 -fPIC -shared --offload-arch=$(ARCH) -Iinclude -Wall -Wno-unused-function $< -o $@
 
 # the device wire decoder (nw_wiredec.hpp) and the host placement (nw_wireplace.hpp) compiled for

@@ -334,6 +334,15 @@ NW_HD void sc_half_split(sc_half& out, const sc& k) {
 #pragma unroll
   for (int i = 0; i < 5; ++i) { xt[i] = 0; yt[i] = i == 0 ? 1u : 0u; }
   bool yneg = false, done = false;
+  // The result starts as the trivial vector (k, 1), so that no path leaves a word of it
+  // unwritten: with `out` first written after the loop, the gfx950 build of the scalar phase
+  // returned X - Y's u beside the fallback's v = 1 for k = l - 1 (u != v k mod 8l;
+  // tests/test_gpu_sc_ops.py, "k listed5").
+#pragma unroll
+  for (int i = 0; i < 8; ++i) out.u[i] = k.w[i];
+#pragma unroll
+  for (int i = 0; i < 5; ++i) out.v[i] = i == 0 ? 1u : 0u;
+  out.vneg = false;
 #pragma unroll 1
   for (int it = 0; it < 400; ++it) {
     done = (yr[4] | yr[5] | yr[6] | yr[7]) == 0;
@@ -462,8 +471,9 @@ NW_HD void sc_half_split(sc_half& out, const sc& k) {
       }
     }
   }
-  // Fallback (iteration cap, or u >= 2^252 / |v| >= 2^160): the trivial vector (k, 1).
-  if (!done || (out.u[7] >> 28) != 0) {
+  // Fallback: at the iteration cap `out` still is the trivial vector (k, 1); a vector with
+  // u >= 2^252 is replaced by it.
+  if ((out.u[7] >> 28) != 0) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) out.u[i] = k.w[i];
 #pragma unroll

@@ -11,6 +11,8 @@ import pytest
 
 from oracle import oracle as O
 
+from sc_cases import constructed_k
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "tools", "libnw_hostcheck.so")
 L = 2**252 + 27742317777372353535851937790883648493
@@ -115,8 +117,12 @@ def _half(hc, k: int):
 
 
 def _adversarial_k():
-    """k whose continued fraction of k / 8l has a huge partial quotient near the stopping
-    point (forces the iteration cap / fallback path)."""
+    """Edge k of the half-size split. Only 2**128 reaches the iteration cap (a 128-bit quotient
+    at the first step); the first two entries are 125- and 128-bit numbers and, like 2**128 - 1,
+    0, 1, 2 and 7, leave before the loop starts with (k, 1); l - 1 and 2**252 end after one
+    step with an even cofactor and a vector too long to use. k
+    with a partial quotient of a chosen size at a chosen depth are tests/sc_cases.py's
+    constructed_k()."""
     n = 8 * L_ORDER
     return [(n * (2**126 + 1)) // (2**128 + 3) % L_ORDER, n // (2**127 + 1) % L_ORDER,
             (2**128 - 1), 2**128, 2**252, L_ORDER - 1, 0, 1, 2, 7]
@@ -144,10 +150,13 @@ def test_half_split_lattice(hc):
 
 def test_half_split_lehmer_equals_one_step(hc):
     """The Lehmer rounds (Knuth Algorithm L, nw_scalar.hpp) only batch exact Euclid steps:
-    the split equals the one-step loop's on random and adversarial k."""
+    the split equals the one-step loop's on random, edge and constructed k (a partial quotient
+    of 2^31 - 1 .. 2^45 at depth 0, 1, 5, 20 and 50 of 8l / k's continued fraction). On this
+    build a lane never waits for a wave, so the two agree in every band."""
     rng = np.random.Generator(np.random.PCG64(14))
     ks = [int.from_bytes(rng.bytes(32), "little") % L_ORDER for _ in range(4000)]
     ks += _adversarial_k() + [2**129 + 5, 3 * 2**127, 2**200 + 1, (8 * L_ORDER) // 3 % L_ORDER]
+    ks += list(constructed_k().values())
     for k in ks:
         outs = []
         for f in (hc.hc_half_split, hc.hc_half_split_onestep):

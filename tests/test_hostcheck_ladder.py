@@ -16,6 +16,7 @@ import pytest
 
 from oracle import oracle as O
 
+from sc_cases import constructed_k
 from test_hostcheck import LIB, L_ORDER, _adversarial_k, _b, _build, _out
 
 BWS = [-16, -24]
@@ -80,12 +81,14 @@ def _scalar_a(seed: bytes) -> int:
 
 
 def _injected_k(hc):
-    """The adversarial k of test_hostcheck.py, random k, and k whose split falls back to
-    the trivial vector (k, 1) (a ladder of up to 64 windows)."""
+    """The edge k of test_hostcheck.py, random k, tests/sc_cases.py's constructed k (a partial
+    quotient of 2^31 - 1 .. 2^45 at five depths of 8l / k's continued fraction), and among them
+    k whose split falls back to the trivial vector (k, 1) (a ladder of up to 64 windows)."""
     rng = np.random.Generator(np.random.PCG64(77))
     ks = [k % L_ORDER for k in _adversarial_k()]
     ks += [2**129 + 5, 3 * 2**127, 2**200 + 1, (8 * L_ORDER) // 3 % L_ORDER]
     ks += [int.from_bytes(rng.bytes(32), "little") % L_ORDER for _ in range(24)]
+    ks += list(constructed_k().values())
     fallback = []
     for k in ks:
         u, v = _out(32), _out(20)

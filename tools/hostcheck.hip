@@ -9,6 +9,7 @@
 #include "../narwhal_amd/csrc/nw_ladder.hpp"
 #include "../narwhal_amd/csrc/nw_strict_keymajor.hpp"
 #include "limb_ops.hpp"
+#include "sc_ops.hpp"
 
 using namespace nw;
 
@@ -853,6 +854,18 @@ int hc_ge_ops(int op, uint32_t n, const uint32_t* A, const uint32_t* B, const in
   if (op < OP_GE_DBL) return -1;
   for (uint32_t i = 0; i < n; ++i)
     if (!limb_op(op, A + 40 * (size_t)i, B + 40 * (size_t)i, k[i], out + 40 * (size_t)i)) return -1;
+  return 0;
+}
+
+// The scalar layer and the scalar phase on raw words (tools/sc_ops.hpp: the operation codes and
+// the 24-word input / 40-word output layout), n cases of one operation per call
+// (tests/test_sc_ops_cpu.py). out is zeroed first. Returns 0, or -1 for an operation code or a
+// key width the dispatcher does not serve.
+int hc_sc_ops(int op, uint32_t n, const uint32_t* in, const int32_t* k, uint32_t* out) {
+  if (op < 0 || op >= SC_N) return -1;
+  memset(out, 0, 4 * (size_t)kScOut * n);
+  for (uint32_t i = 0; i < n; ++i)
+    if (!sc_op(op, in + kScIn * (size_t)i, k[i], out + kScOut * (size_t)i)) return -1;
   return 0;
 }
 

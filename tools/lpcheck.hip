@@ -6,6 +6,9 @@
 //
 //   k_fe_ops  one lane per case: tools/limb_ops.hpp's operation codes, as hc_fe_ops /
 //             hc_ge_ops run them on the CPU build of the same text.
+//   k_sc_ops  one lane per case: tools/sc_ops.hpp's operation codes over the scalar layer
+//             (nw_scalar.hpp, the scalar phase of nw_strict.hpp), as hc_sc_ops runs them on
+//             the CPU build, for tests/test_gpu_sc_ops.py.
 //   k_lp_ops  one wave per case: operands are four planes of 64 words (plane p, lane l at
 //             word 64 p + l; lane 16 r + k = limb k of row r), the output likewise.
 // Both run at any block size that is a multiple of 64 with lane = tid & 63 (the product calls
@@ -14,6 +17,7 @@
 #include <stdint.h>
 #include "../narwhal_amd/csrc/nw_lp.hpp"
 #include "limb_ops.hpp"
+#include "sc_ops.hpp"
 
 using namespace nw;
 
@@ -46,6 +50,17 @@ __global__ __launch_bounds__(64 * kLpWavesMax) void k_fe_ops(
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   if (!limb_op(op, A + 40 * i, B + 40 * i, k[i], out + 40 * i)) *bad = 1u;
+}
+
+// One lane per case, lane = case index: the order of the cases decides which share a wave (the
+// half-size split's one-step code runs only in an iteration where no lane of the wave made
+// Lehmer progress, nw_scalar.hpp nw_any).
+__global__ __launch_bounds__(64 * kLpWavesMax) void k_sc_ops(
+    int op, uint32_t n, const uint32_t* __restrict__ in, const int32_t* __restrict__ k,
+    uint32_t* __restrict__ out, uint32_t* __restrict__ bad) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (!sc_op(op, in + kScIn * i, k[i], out + kScOut * i)) *bad = 1u;
 }
 
 __global__ __launch_bounds__(64 * kLpWavesMax) void k_lp_ops(
@@ -143,6 +158,29 @@ int lpc_fe_ops(int op, uint32_t n, const uint32_t* A, const uint32_t* B, const i
   uint32_t bad = 0;
   LPC_TRY(hipMemcpy(&bad, dbad.p, 4, hipMemcpyDeviceToHost));
   LPC_TRY(hipMemcpy(out, dout.p, 4 * words, hipMemcpyDeviceToHost));
+  return bad ? -1 : 0;
+}
+
+// n cases of one sc_ops.hpp operation, one lane each (lane = case index & 63): in n x 24 words,
+// k n integers, out n x 40 words.
+int lpc_sc_ops(int op, uint32_t n, const uint32_t* in, const int32_t* k, uint32_t* out, int block) {
+  if (!block_ok(block) || n == 0 || n > (1u << 24) || op < 0 || op >= SC_N) return -1;
+  const size_t wi = kScIn * (size_t)n, wo = kScOut * (size_t)n;
+  dev_buf din, dk, dout, dbad;
+  LPC_TRY(din.alloc(4 * wi)); LPC_TRY(dk.alloc(4 * (size_t)n));
+  LPC_TRY(dout.alloc(4 * wo)); LPC_TRY(dbad.alloc(4));
+  LPC_TRY(hipMemcpy(din.p, in, 4 * wi, hipMemcpyHostToDevice));
+  LPC_TRY(hipMemcpy(dk.p, k, 4 * (size_t)n, hipMemcpyHostToDevice));
+  LPC_TRY(hipMemset(dout.p, 0, 4 * wo));
+  LPC_TRY(hipMemset(dbad.p, 0, 4));
+  const uint32_t grid = (uint32_t)(((uint64_t)n + block - 1) / block);
+  hipLaunchKernelGGL(k_sc_ops, dim3(grid), dim3(block), 0, 0, op, n, din.as<uint32_t>(),
+                     dk.as<int32_t>(), dout.as<uint32_t>(), dbad.as<uint32_t>());
+  LPC_TRY(hipGetLastError());
+  LPC_TRY(hipDeviceSynchronize());
+  uint32_t bad = 0;
+  LPC_TRY(hipMemcpy(&bad, dbad.p, 4, hipMemcpyDeviceToHost));
+  LPC_TRY(hipMemcpy(out, dout.p, 4 * wo, hipMemcpyDeviceToHost));
   return bad ? -1 : 0;
 }
 
