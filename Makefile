@@ -120,6 +120,13 @@ hramsan: tools/hram_lane_san
 tools/hram_lane_san: tools/hram_lane_san.cpp tools/hram_san/hip/hip_runtime.h $(CSRC)/nw_sha512.hpp $(CSRC)/nw_field.hpp
 	$(CLANGXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -Itools/hram_san -I$(CSRC) $< -o $@
 
+# the same routine's 32-byte-prefix instance (sha512_prefix_lane<8>: prefix || M, the hash behind
+# r of signing over messages of any length), built the same way (not part of `all`;
+# tests/test_sha512_prefix_cpu.py builds and runs it)
+prefixsan: tools/prefix_lane_san
+tools/prefix_lane_san: tools/prefix_lane_san.cpp tools/hram_san/hip/hip_runtime.h $(CSRC)/nw_sha512.hpp $(CSRC)/nw_field.hpp
+	$(CLANGXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -Itools/hram_san -I$(CSRC) $< -o $@
+
 loadgen: tools/libnw_loadgen.so
 tools/libnw_loadgen.so: tools/nw_loadgen.cpp include/narwhal_amd.h $(LIB)
 	g++ -O2 -std=c++17 -fPIC -shared -Iinclude $< -o $@ -Lnarwhal_amd -lnarwhal_amd -Wl,-rpath,'$$ORIGIN/../narwhal_amd' -pthread
@@ -138,7 +145,7 @@ tools/ubench_valu: tools/ubench_valu.hip
 	$(HIPCC) --offload-arch=$(ARCH) -O3 $< -o $@
 
 clean:
-	rm -rf $(BUILD) $(LIB) tools/libnw_hostcheck.so tools/libnw_lpcheck.so tools/libnw_wirecheck.so tools/libnw_stagecheck.so tools/libnw_batchcheck.so tools/libnw_loadgen.so tools/service_stress tools/service_stress_tsan tools/wire_canon_san tools/stage_san tools/batch_san tools/keyset_san tools/hram_lane_san
+	rm -rf $(BUILD) $(LIB) tools/libnw_hostcheck.so tools/libnw_lpcheck.so tools/libnw_wirecheck.so tools/libnw_stagecheck.so tools/libnw_batchcheck.so tools/libnw_loadgen.so tools/service_stress tools/service_stress_tsan tools/wire_canon_san tools/stage_san tools/batch_san tools/keyset_san tools/hram_lane_san tools/prefix_lane_san
 	$(MAKE) -s -C oracle clean
 
-.PHONY: all oracle hostcheck lpcheck wirecheck stagecheck batchcheck batchsan wiresan stagesan keysetsan hramsan loadgen stress ubench clean
+.PHONY: all oracle hostcheck lpcheck wirecheck stagecheck batchcheck batchsan wiresan stagesan keysetsan hramsan prefixsan loadgen stress ubench clean

@@ -203,6 +203,21 @@ int nw_keypair_from_seed_many(const uint8_t* seeds, size_t n, uint8_t* pks_out);
 int nw_sign_many(const uint8_t* sks, size_t sk_stride, const uint8_t* digests,
                  size_t digest_stride, size_t n, uint8_t* sigs_out);
 
+/* Signing over messages of any length: ed25519_dalek::Keypair::sign(&[u8]), the call behind
+ * crypto::Signature::new (crypto/src/lib.rs:185-191), which hands it a 32-byte digest; here the
+ * message is the caller's own bytes (deterministic, RFC 8032 5.1.6). Message i is lengths[i]
+ * bytes at data + offsets[i], as in nw_verify_strict_msgs_many: any alignment; gaps, overlaps
+ * and any order are allowed; lengths is required; data may be null when every message is empty.
+ * sks: n x 64 bytes (seed || pk; the second half is used as A as given), sk_stride = 64, or one
+ * key that signs every message (sk_stride = 0). sigs_out: n x 64 bytes. For 32-byte messages the
+ * output equals nw_sign_many's byte for byte. Both hashes run on the item's lane, so the entry is
+ * meant for messages of up to a few KB. Runs on one device (NW_E_INVALID_ARG under
+ * NW_ALL_DEVICES, as nw_sign_many); NW_E_OUT_OF_MEMORY when a staging buffer cannot grow, after
+ * which the library stays usable. */
+int nw_sign_msgs_many(const uint8_t* sks, size_t sk_stride, const uint8_t* data,
+                      const uint64_t* offsets, const uint64_t* lengths, size_t n,
+                      uint8_t* sigs_out);
+
 /* ---- asynchronous host-buffer entry points (submit / poll) ------------------------- */
 /* The non-blocking form of the calls above, for callers that must not block their event
  * loop (the reference's primary Core and worker Processor are tokio tasks, node/Cargo.toml:8;
@@ -582,6 +597,15 @@ int nw_dev_keypair_from_seed_many(const void* seeds, size_t n, void* pks_out, vo
 
 int nw_dev_sign_many(const void* sks, size_t sk_stride, const void* digests,
                      size_t digest_stride, size_t n, void* sigs_out, void* stream);
+
+/* Device form of nw_sign_msgs_many (ed25519_dalek::Keypair::sign(&[u8]), the call behind
+ * crypto/src/lib.rs:185-191): sks, data, offsets, lengths and sigs_out are device pointers. One
+ * launch is queued on `stream` (null: the calling thread's own) and the call returns; it uses no
+ * buffer of the library's, so launches on several streams may overlap. For 32-byte messages the
+ * output equals nw_dev_sign_many's byte for byte. */
+int nw_dev_sign_msgs_many(const void* sks, size_t sk_stride, const void* data,
+                          const uint64_t* offsets, const uint64_t* lengths, size_t n,
+                          void* sigs_out, void* stream);
 
 /* Workspace bytes nw_dev_verify_batch_many needs for nbatches batches of nitems votes in
  * total (bounded: large calls are processed in slices of ~4M votes; a single batch may not

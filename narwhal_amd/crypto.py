@@ -9,14 +9,15 @@ behaviour, so code (and tests) written against the Rust crate read the same here
     Signature(part1, part2), flatten      lib.rs:177-198
     Signature.verify(digest, pk)          lib.rs:200-204  -> raises CryptoError
     Signature.verify_batch(digest, votes) lib.rs:206-219  -> raises CryptoError
+    Signature.new_message(msg, secret)    dalek's Keypair::sign(&[u8]): a message of any length
     Signature.verify_message(msg, pk)     dalek's verify_strict(&[u8]): a message of any length
     Signature.verify_batch_messages(items) dalek's verify_batch(messages, signatures, keys)
     CryptoError                           lib.rs:18 (ed25519::Error, opaque)
 
 Every check runs in the gfx950 kernels through the C ABI (include/narwhal_amd.h); there
 is no CPU path. Runtime/device failures raise EngineError, never CryptoError.
-Bulk helpers (verify_strict_many, verify_strict_msgs_many, verify_batch_many,
-verify_batch_msgs_many, sha512_digest32_many) expose the
+Bulk helpers (sign_many, sign_msgs_many, verify_strict_many, verify_strict_msgs_many,
+verify_batch_many, verify_batch_msgs_many, sha512_digest32_many) expose the
 batched entry points the aggregation service uses.
 """
 from __future__ import annotations
@@ -33,6 +34,7 @@ from ._lib import EngineError, check
 
 __all__ = ["Digest", "Hash", "PublicKey", "SecretKey", "Signature", "CryptoError",
            "EngineError", "generate_keypair", "keypair_from_seed_many", "sign_many",
+           "sign_msgs_many",
            "sha512_digest", "sha512_digest32_many", "verify_strict_many",
            "verify_strict_msgs_many",
            "verify_batch_many", "verify_batch_msgs_many", "set_strict_signers", "strict_signers_count",
@@ -158,6 +160,23 @@ def sign_many(sks: np.ndarray, digests: np.ndarray, shared_key: bool = False,
     return out
 
 
+def sign_msgs_many(sks: np.ndarray, messages, shared_key: bool = False) -> np.ndarray:
+    """n x dalek's Keypair::sign over messages of any length (nw_sign_msgs_many; RFC 8032,
+    deterministic). ``messages`` is a list of bytes, or the (data, offsets, lengths) arrays as in
+    verify_strict_msgs_many; ``sks`` is n x 64 bytes, or one key for every message with
+    ``shared_key``. Returns n x 64 bytes; for 32-byte messages they equal sign_many's."""
+    data, offsets, lengths = _message_arrays(messages)
+    sks = np.ascontiguousarray(sks, dtype=np.uint8).reshape(-1, 64)
+    n = len(offsets)
+    if len(lengths) != n or sks.shape[0] != (1 if shared_key else n):
+        raise ValueError("sks and messages must name the same number of items")
+    out = np.zeros((n, 64), np.uint8)
+    check(_lib.lib().nw_sign_msgs_many(_ptr(sks), 0 if shared_key else 64, _ptr(data),
+                                       _ptr(offsets), _ptr(lengths), n, _ptr(out)),
+          "nw_sign_msgs_many")
+    return out
+
+
 @dataclass(frozen=True)
 class Signature:
     part1: bytes = bytes(32)   # R
@@ -175,6 +194,14 @@ class Signature:
         sig = sign_many(np.frombuffer(bytes(secret), np.uint8),
                         np.frombuffer(digest.value, np.uint8), shared_key=True,
                         shared_digest=True)[0].tobytes()
+        return cls.from_bytes(sig)
+
+    @classmethod
+    def new_message(cls, message: bytes, secret: SecretKey) -> "Signature":
+        """ed25519_dalek's Keypair::sign(message) over the message's own bytes, of any length
+        (Signature.new is the same signature of a 32-byte Digest)."""
+        sig = sign_msgs_many(np.frombuffer(bytes(secret), np.uint8), [bytes(message)],
+                             shared_key=True)[0].tobytes()
         return cls.from_bytes(sig)
 
     def flatten(self) -> bytes:

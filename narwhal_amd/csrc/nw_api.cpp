@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
+#include <exception>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -22,8 +23,10 @@
 #include "narwhal_amd.h"
 #include "nw_kernels.h"
 #include "nw_runtime.h"
+#include "nw_stage.hpp"
 
 namespace {
+namespace stg = nw::stage;
 
 constexpr int kMaxDevices = 64;
 
@@ -494,6 +497,67 @@ int nw_sign_many(const uint8_t* sks, size_t sk_stride, const uint8_t* digests,
                          reinterpret_cast<const uint32_t*>(d_m), (uint32_t)(digest_stride / 4),
                          n, reinterpret_cast<uint32_t*>(d_s), s), "k_sign launch");
   NW_HIP(hipMemcpyAsync(sigs_out, d_s, 64 * n, hipMemcpyDeviceToHost, s), "D2H sigs");
+  NW_HIP(hipStreamSynchronize(s), "sync");
+  return 0;
+}
+
+int nw_dev_sign_msgs_many(const void* sks, size_t sk_stride, const void* data,
+                          const uint64_t* offsets, const uint64_t* lengths, size_t n,
+                          void* sigs_out, void* stream) {
+  DevCtx* c;
+  int rc = begin(&c);
+  if (rc) return rc;
+  if (n && (!sks || !offsets || !lengths || !sigs_out))
+    return set_err(NW_E_INVALID_ARG, "null pointer (lengths is required)");
+  if (sk_stride != 0 && sk_stride != 64)
+    return set_err(NW_E_INVALID_ARG, "sk_stride must be 0 or 64");
+  NW_HIP(nw::launch_sign_msgs(static_cast<const uint32_t*>(sks), (uint32_t)(sk_stride / 4),
+                              static_cast<const uint8_t*>(data), offsets, lengths, n,
+                              static_cast<uint32_t*>(sigs_out), pick_stream(stream, c)),
+         "k_sign_msgs launch");
+  return 0;
+}
+
+// The messages packed in item order (stg::pack_messages) into the thread's host staging buffer
+// together with their offsets and lengths, one copy up for the three, one for the keys, one
+// launch, the copy down.
+int nw_sign_msgs_many(const uint8_t* sks, size_t sk_stride, const uint8_t* data,
+                      const uint64_t* offsets, const uint64_t* lengths, size_t n,
+                      uint8_t* sigs_out) {
+  DevCtx* c;
+  int rc = begin(&c);
+  if (rc) return rc;
+  if (n == 0) return 0;
+  if (!sks || !offsets || !lengths || !sigs_out)
+    return set_err(NW_E_INVALID_ARG, "null pointer (lengths is required)");
+  if (sk_stride != 0 && sk_stride != 64)
+    return set_err(NW_E_INVALID_ARG, "sk_stride must be 0 or 64");
+  const uint64_t total = stg::messages_bytes(lengths, n);
+  if (total && !data) return set_err(NW_E_INVALID_ARG, "null data with a non-empty message");
+  const size_t nk = sk_stride ? n : 1;
+  const size_t o_off = a256(total ? total : 1), o_len = o_off + a256(8 * n),
+               o_k = o_len + a256(8 * n), o_s = o_k + a256(64 * nk), end = o_s + a256(64 * n);
+  static thread_local std::vector<char> t_stage;   // [0, o_k): messages, offsets, lengths
+  try {
+    if (t_stage.size() < o_k) t_stage.resize(o_k + o_k / 4);
+  } catch (const std::exception&) {   // bad_alloc, or length_error beyond max_size
+    return set_err(NW_E_OUT_OF_MEMORY, "host staging buffer of nw_sign_msgs_many");
+  }
+  rc = reserve(*c, end);
+  if (rc) return rc;
+  char* const h = t_stage.data();
+  stg::pack_messages(h, reinterpret_cast<uint64_t*>(h + o_off), data, offsets, lengths, n);
+  memcpy(h + o_len, lengths, 8 * n);
+  uint8_t* const d = static_cast<uint8_t*>(c->dbuf);
+  hipStream_t s = c->stream;
+  NW_HIP(hipMemcpyAsync(d, h, o_k, hipMemcpyHostToDevice, s), "H2D messages");
+  NW_HIP(hipMemcpyAsync(d + o_k, sks, 64 * nk, hipMemcpyHostToDevice, s), "H2D sks");
+  NW_HIP(nw::launch_sign_msgs(reinterpret_cast<const uint32_t*>(d + o_k),
+                              (uint32_t)(sk_stride / 4), d,
+                              reinterpret_cast<const uint64_t*>(d + o_off),
+                              reinterpret_cast<const uint64_t*>(d + o_len), n,
+                              reinterpret_cast<uint32_t*>(d + o_s), s), "k_sign_msgs launch");
+  NW_HIP(hipMemcpyAsync(sigs_out, d + o_s, 64 * n, hipMemcpyDeviceToHost, s), "D2H sigs");
   NW_HIP(hipStreamSynchronize(s), "sync");
   return 0;
 }

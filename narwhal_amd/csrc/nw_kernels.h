@@ -204,6 +204,16 @@ hipError_t launch_sign(const uint32_t* sks, uint32_t sk_stride_words, const uint
                        uint32_t msg_stride_words, uint64_t n, uint32_t* sigs,
                        hipStream_t stream);
 
+// k_sign_msgs: RFC 8032 signatures over messages of any length. Message i is lengths[i] bytes at
+// data + offsets[i] (device arrays; any alignment; data may be null when every message is empty);
+// sks as launch_sign takes them (seed || public key, stride 16 words, or 0 = one key for every
+// message). Both hashes run on the item's lane over the message itself, which is read twice. One
+// lane per item, and a wave runs as long as its longest message: meant for messages of up to a
+// few KB, like launch_strict_hram.
+hipError_t launch_sign_msgs(const uint32_t* sks, uint32_t sk_stride_words, const uint8_t* data,
+                            const uint64_t* offsets, const uint64_t* lengths, uint64_t n,
+                            uint32_t* sigs, hipStream_t stream);
+
 // crypto::Signature::verify_batch over many batches (nw_batch.hip). offsets: device copy,
 // host_offsets: the same nbatches + 1 values in host memory (used to plan the chunks and
 // the workspace slices).

@@ -1538,6 +1538,52 @@ __global__ __launch_bounds__(256) void k_sign(const uint32_t* __restrict__ sks,
   }
 }
 
+// The same over messages of any length (RFC 8032 5.1.6, dalek's Keypair::sign(&[u8])): message i
+// is lengths[i] bytes at data + offsets[i], any alignment. Both hashes are sha512_prefix_lane's
+// (nw_sha512.hpp): r over prefix || M (8-word prefix), k over R || A || M (16 words), so M is read
+// twice, the second time from cache. A is the key's second half as given, as in k_sign. One lane
+// per item; a wave runs as long as its longest message.
+__global__ __launch_bounds__(256) void k_sign_msgs(const uint32_t* __restrict__ sks,
+                                                   uint32_t sk_stride_words,
+                                                   const uint8_t* __restrict__ data,
+                                                   const uint64_t* __restrict__ offsets,
+                                                   const uint64_t* __restrict__ lengths,
+                                                   uint64_t n, uint32_t* __restrict__ sigs) {
+  __shared__ ge_niels s_btab[129];
+  load_btab(s_btab);
+  __syncthreads();
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t seed[8], pk[8], prefix[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    seed[j] = sks[(uint64_t)sk_stride_words * i + j];
+    pk[j] = sks[(uint64_t)sk_stride_words * i + 8 + j];
+  }
+  const uint8_t* const msg = data + offsets[i];
+  const uint64_t len = lengths[i];
+  sc a;
+  expand_seed(a, prefix, seed);
+  uint32_t hx[16];
+  sha512_prefix_lane<8>(hx, prefix, msg, len);
+  sc r;
+  sc_reduce512(r, hx);
+  ge R;
+  fixed_base_mul(R, r, s_btab);
+  uint32_t Rw[8];
+  ge_tobytes(Rw, R);
+  sha512_hram_lane(hx, Rw, pk, msg, len);
+  sc k, ka, s;
+  sc_reduce512(k, hx);
+  sc_mul(ka, k, a);
+  sc_add(s, ka, r);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    sigs[16 * i + j] = Rw[j];
+    sigs[16 * i + 8 + j] = s.w[j];
+  }
+}
+
 }  // namespace nw
 
 namespace nw {
@@ -2369,6 +2415,16 @@ hipError_t launch_sign(const uint32_t* sks, uint32_t sk_stride_words, const uint
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_sign, dim3(grid_for(n, 256)), dim3(256), 0, stream, sks, sk_stride_words,
                      msgs, msg_stride_words, n, sigs);
+  return hipGetLastError();
+}
+
+hipError_t launch_sign_msgs(const uint32_t* sks, uint32_t sk_stride_words, const uint8_t* data,
+                            const uint64_t* offsets, const uint64_t* lengths, uint64_t n,
+                            uint32_t* sigs, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  if (!sks || !offsets || !lengths || !sigs) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_sign_msgs, dim3(grid_for(n, 256)), dim3(256), 0, stream, sks,
+                     sk_stride_words, data, offsets, lengths, n, sigs);
   return hipGetLastError();
 }
 

@@ -254,26 +254,29 @@ __device__ __forceinline__ void sha512_hram96(uint32_t x[16], const uint32_t R[8
   }
 }
 
-// The second half of block 0 of R || A || msg for a message shorter than the half (len < 64):
-// words 8..15 = the message bytes, 0x80, zeros and, when the padding fits (last: len <= 47), the
-// bit length of the 64 + len bytes. load_block_tail's read rule with the block's start at the
-// message's: an aligned dword is loaded only when it holds a message byte, so nothing is read
-// for len = 0 (there the dword below a misaligned msg holds none).
-__device__ __forceinline__ void load_half_tail(uint64_t w[16], const uint8_t* msg, uint64_t len,
-                                               bool last) {
+// The message part of block 0 of P || msg for a prefix P of PW words (8 or 16: a quarter or half
+// of the block) and a message shorter than that part (len < 128 - 4 PW): words PW / 2 .. 15 = the
+// message bytes, 0x80, zeros and, when the padding fits (last: 4 PW + len <= 111), the bit length
+// of the 4 PW + len bytes. load_block_tail's read rule with the block's start at the message's:
+// an aligned dword is loaded only when it holds a message byte, so nothing is read for len = 0
+// (there the dword below a misaligned msg holds none).
+template <int PW>
+__device__ __forceinline__ void load_prefix_tail(uint64_t w[16], const uint8_t* msg, uint64_t len,
+                                                 bool last) {
+  constexpr int MD = 32 - PW;   // dwords of the block behind the prefix
   const uintptr_t a0 = (uintptr_t)msg;
   const uint32_t* q = reinterpret_cast<const uint32_t*>(a0 & ~(uintptr_t)3);
   const uint32_t sh = (uint32_t)(a0 & 3) * 8;
   const int64_t rem = (int64_t)len;
-  // dword q[i] covers half bytes [4 i - sh/8, 4 i - sh/8 + 4), of which the last is >= 0
-  uint32_t qd[17];
+  // dword q[i] covers part bytes [4 i - sh/8, 4 i - sh/8 + 4), of which the last is >= 0
+  uint32_t qd[MD + 1];
 #pragma unroll
-  for (int i = 0; i < 17; ++i) {
+  for (int i = 0; i < MD + 1; ++i) {
     const int64_t first = 4 * (int64_t)i - (int64_t)(sh >> 3);
     qd[i] = (rem > 0 && first < rem) ? q[i] : 0u;
   }
 #pragma unroll
-  for (int i = 1; i < 17; ++i) {
+  for (int i = 1; i < MD + 1; ++i) {
     uint32_t lo = __builtin_amdgcn_alignbit(qd[i], qd[i - 1], sh);
     const int64_t k0 = 4 * (int64_t)(i - 1);
     uint32_t keep = 0, pad = 0;
@@ -284,69 +287,73 @@ __device__ __forceinline__ void load_half_tail(uint64_t w[16], const uint8_t* ms
       pad |= (pos == rem ? 0x80u : 0u) << (8 * b);
     }
     lo = (lo & keep) | pad;
-    const int wi = 8 + ((i - 1) >> 1);
+    const int wi = PW / 2 + ((i - 1) >> 1);
     const uint64_t be = (uint64_t)__builtin_bswap32(lo);
     if ((i - 1) & 1) w[wi] = (w[wi] & 0xffffffff00000000ull) | be;
     else w[wi] = be << 32;
   }
   if (last) {
     w[14] = 0;
-    w[15] = (64 + len) << 3;
+    w[15] = (4 * PW + len) << 3;
   }
 }
 
-// SHA-512(R || A || msg[0..len)) on one lane -> 16 LE words of the digest: the hash whose
-// reduction mod l is Ed25519's k, for a message of any length at any byte address. The 64-byte
-// prefix is half a block, so block 0 is R || A || msg[0..64) and block k >= 1 is
-// msg[128 k - 64 .. 128 k + 64): every block starts at msg's alignment, and the full ones are
-// load_block_raw's, double-buffered as in sha512_digest32_lane. The padding is that of a message
-// of 64 + len bytes (load_block_tail on the address 64 bytes below msg, which it only adds to:
-// blocks k >= 1 start inside the message): 0x80 after the last byte, the bit length
-// (64 + len) * 8 in the last 16 bytes, a padding-only block when (64 + len) mod 128 > 111.
-// Only aligned dwords that hold a message byte are read; nothing is read for len = 0.
-__device__ __forceinline__ void sha512_hram_lane(uint32_t x[16], const uint32_t R[8],
-                                                 const uint32_t A[8], const uint8_t* msg,
-                                                 uint64_t len) {
-  const uint64_t total = 64 + len;
+// SHA-512(P || msg[0..len)) on one lane -> 16 LE words of the digest, for a prefix P of PW LE
+// words (8 or 16) and a message of any length at any byte address. PW = 16, P = R || A: the hash
+// whose reduction mod l is Ed25519's k (sha512_hram_lane below); PW = 8, P = the expanded secret's
+// second half: the hash whose reduction mod l is RFC 8032's r (k_sign_msgs). The prefix is a
+// quarter or half of a block, so block 0 is P || msg[0..MB) with MB = 128 - 4 PW (96 or 64) and
+// block k >= 1 is msg[128 k - 4 PW .. 128 k + MB): 4 PW is a multiple of 4, so every block starts
+// at msg's alignment, and the full ones are load_block_raw's, double-buffered as in
+// sha512_digest32_lane. The padding is that of a message of 4 PW + len bytes (load_block_tail on
+// the address 4 PW bytes below msg, which it only adds to: blocks k >= 1 start inside the
+// message): 0x80 after the last byte, the bit length (4 PW + len) * 8 in the last 16 bytes, a
+// padding-only block when (4 PW + len) mod 128 > 111. Only aligned dwords that hold a message
+// byte are read; nothing is read for len = 0.
+template <int PW>
+__device__ __forceinline__ void sha512_prefix_lane(uint32_t x[16], const uint32_t* P,
+                                                   const uint8_t* msg, uint64_t len) {
+  static_assert(PW == 8 || PW == 16, "the prefix is a quarter or half of a block");
+  constexpr int MD = 32 - PW;    // dwords of block 0 behind the prefix
+  constexpr int MB = 4 * MD;     // their bytes
+  const uint64_t total = 4 * PW + len;
   const uint64_t nblocks = (total + 17 + 127) / 128;
-  const uint64_t nfull = total / 128;   // blocks without padding; block 0 is one when len >= 64
+  const uint64_t nfull = total / 128;   // blocks without padding; block 0 is one when len >= MB
   const uint32_t sh = (uint32_t)((uintptr_t)msg & 3) * 8;
   uint64_t st[8], w[16];
   sha512_init(st);
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    w[i] = ((uint64_t)__builtin_bswap32(R[2 * i]) << 32) | __builtin_bswap32(R[2 * i + 1]);
-    w[4 + i] = ((uint64_t)__builtin_bswap32(A[2 * i]) << 32) | __builtin_bswap32(A[2 * i + 1]);
-  }
+  for (int i = 0; i < PW / 2; ++i)
+    w[i] = ((uint64_t)__builtin_bswap32(P[2 * i]) << 32) | __builtin_bswap32(P[2 * i + 1]);
   if (nfull) {
     uint32_t d[33];
     {
-      // msg[0..64): the 17 aligned dwords that cover it (the 17th only when msg is misaligned)
+      // msg[0..MB): the MD + 1 aligned dwords that cover it (the last only when msg is misaligned)
       const uintptr_t a = (uintptr_t)msg;
       const uint32_t* q = reinterpret_cast<const uint32_t*>(a & ~(uintptr_t)3);
 #pragma unroll
-      for (int i = 0; i < 16; ++i) d[i] = q[i];
-      d[16] = (a & 3) ? q[16] : 0u;
+      for (int i = 0; i < MD; ++i) d[i] = q[i];
+      d[MD] = (a & 3) ? q[MD] : 0u;
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
+      for (int i = 0; i < MD / 2; ++i) {
         const uint32_t lo = __builtin_amdgcn_alignbit(d[2 * i + 1], d[2 * i], sh);
         const uint32_t hi = __builtin_amdgcn_alignbit(d[2 * i + 2], d[2 * i + 1], sh);
-        w[8 + i] = ((uint64_t)__builtin_bswap32(lo) << 32) | __builtin_bswap32(hi);
+        w[PW / 2 + i] = ((uint64_t)__builtin_bswap32(lo) << 32) | __builtin_bswap32(hi);
       }
     }
-    if (nfull > 1) load_block_raw(d, msg + 64);
+    if (nfull > 1) load_block_raw(d, msg + MB);
     sha512_compress(st, w);
 #pragma unroll 1
     for (uint64_t k = 1; k < nfull; ++k) {
       block_from_raw(w, d, sh);
-      if (k + 1 < nfull) load_block_raw(d, msg + 128 * (k + 1) - 64);
+      if (k + 1 < nfull) load_block_raw(d, msg + 128 * (k + 1) - 4 * PW);
       sha512_compress(st, w);
     }
   } else {
-    load_half_tail(w, msg, len, nblocks == 1);
+    load_prefix_tail<PW>(w, msg, len, nblocks == 1);
     sha512_compress(st, w);
   }
-  const uint8_t* const below = reinterpret_cast<const uint8_t*>((uintptr_t)msg - 64);
+  const uint8_t* const below = reinterpret_cast<const uint8_t*>((uintptr_t)msg - 4 * PW);
 #pragma unroll 1
   for (uint64_t k = nfull ? nfull : 1; k < nblocks; ++k) {
     load_block_tail(w, below, 128 * k, total, k + 1 == nblocks);
@@ -357,6 +364,19 @@ __device__ __forceinline__ void sha512_hram_lane(uint32_t x[16], const uint32_t 
     x[2 * i] = __builtin_bswap32((uint32_t)(st[i] >> 32));
     x[2 * i + 1] = __builtin_bswap32((uint32_t)st[i]);
   }
+}
+
+// SHA-512(R || A || msg[0..len)): the 16-word instance of sha512_prefix_lane.
+__device__ __forceinline__ void sha512_hram_lane(uint32_t x[16], const uint32_t R[8],
+                                                 const uint32_t A[8], const uint8_t* msg,
+                                                 uint64_t len) {
+  uint32_t P[16];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    P[j] = R[j];
+    P[8 + j] = A[j];
+  }
+  sha512_prefix_lane<16>(x, P, msg, len);
 }
 
 // Digest(Sha512(x32 || u64 LE || y32)[..32]): Vote::digest / Certificate::digest
